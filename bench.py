@@ -1,6 +1,6 @@
 """bench.py — train-step throughput of the MI355X NeuS hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|...] [--graph]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|...] [--graph] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
     python bench.py --gpus 2 --dry --backend gloo      (launcher check on the CPU, no HIP work)
 
@@ -15,7 +15,12 @@ backward (incl. the ∇ₓSDF double backward), the gradient all-reduce (N > 1)
 and Adam.  Weak scaling: every rank renders its own 4096 rays.  The timed
 steps run uninstrumented.
 
-The JSON line also carries
+A plain run sets up, warms up, times the steps and prints the line.  `--dump-outputs DIR` also
+writes what the last timed step computed (the loss, the gradients and the updated parameters; for
+`--config infer` the rendered maps) as DIR/<name>.npy: the inputs are seeded, so two builds can be
+compared output for output.
+
+With `--full` the JSON line also carries
   roofline      the dominant kernel (the cn_linear / cn_wgrad launch class with the
                 most time), from a separate instrumented pass after the timed steps
                 (HIP events around each launch on the launching stream):
@@ -304,6 +309,43 @@ def dry_step(rank, world, grad_numel=800_000):
     return flat.sum()
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def step_outputs(tr, loss, image=None):
+    """What a caller of the timed step holds after the last one: the rendered maps (inference), or
+    the step's loss, the gradients it left and the parameters Adam wrote (training)."""
+    if image is not None:
+        return dict(image)
+    out = {"loss": loss}
+    names = {}
+    for prefix in ("sdf", "var", "col", "poses", "motion"):
+        mod = getattr(tr, prefix, None)
+        if mod is not None:
+            names.update({id(p): f"{prefix}.{n}" for n, p in mod.named_parameters()})
+    for p in tr.all_params:
+        out["param." + names[id(p)]] = p
+        if p.grad is not None:
+            out["grad." + names[id(p)]] = p.grad
+    return out
+
+
+def dump_outputs(path, tensors):
+    """--dump-outputs: every tensor as <path>/<name>.npy in float32; past DUMP_LIMIT_BYTES in all, the
+    arrays above an equal share are cut to a fixed seeded sample of their flattened elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().to("cpu", torch.float32).numpy() for k, v in tensors.items()}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        share = DUMP_LIMIT_BYTES // len(arrays) // 4
+        rng = np.random.default_rng(0)
+        for k, a in arrays.items():
+            if a.size > share:
+                arrays[k] = a.reshape(-1)[np.sort(rng.choice(a.size, share, replace=False))]
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
@@ -314,8 +356,14 @@ def main():
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2")
     ap.add_argument("--rays", type=int, default=None, help="rays per GPU (default: the config's)")
     ap.add_argument("--graph", action="store_true", help="replay the step from a captured HIP graph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--timer-steps", type=int, default=3, help="instrumented steps after the timed ones (roofline)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the instrumented roofline pass and (c2, one GPU) the CPU "
+                         "baseline; without it `roofline` and `cpu_baseline` are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--timer-steps", type=int, default=3,
+                    help="with --full: instrumented steps after the timed ones (roofline)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="process-group backend (nccl = RCCL over xGMI; gloo only with --dry)")
     ap.add_argument("--dry", action="store_true",
@@ -362,9 +410,11 @@ def main():
     if infer:
         from copenerf.inference import render_image
         t_img = torch.zeros(1, device=f"cuda:{local}")
+        last_image = {}
 
         def step():
             out = render_image(tr.renderer, tr.K, tr.I, tr.I, (tr.H, tr.W), t_img, chunk=65536)
+            last_image.update(out)  # (references only: what --dump-outputs writes)
             return out["rgb"].sum()
     if graph:  # the captured step includes the data-parallel all-reduce (RCCL) when distributed
         g = GraphedTrainer(tr, warmup=max(1, args.warmup))
@@ -389,14 +439,18 @@ def main():
         elapsed = t.item()
     if not torch.isfinite(loss).item():
         raise RuntimeError("non-finite loss in the timed steps")
-    # the roofline pass: separate, instrumented (HIP events around every GEMM), eager
-    timer = ops.KernelTimer()
-    ops.set_kernel_timer(timer)
-    n_inst = max(1, args.timer_steps)
-    for _ in range(n_inst):
-        tr.step() if not infer else step()
-    torch.cuda.synchronize()
-    ops.set_kernel_timer(None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(tr, loss, last_image if infer else None))
+    timer = None
+    if args.full:
+        # the roofline pass: separate, instrumented (HIP events around every GEMM), eager
+        timer = ops.KernelTimer()
+        ops.set_kernel_timer(timer)
+        n_inst = max(1, args.timer_steps)
+        for _ in range(n_inst):
+            tr.step() if not infer else step()
+        torch.cuda.synchronize()
+        ops.set_kernel_timer(None)
 
     rays_total = rays * world * args.steps
     S = 192 if args.config == "c5" else SAMPLES
@@ -429,8 +483,9 @@ def main():
         "roofline": None,
         "cpu_baseline": None,
     }
-    result.update(roofline_fields(timer, n_inst, rays_total / elapsed, mode, args.config))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "c2":
+    if timer is not None:
+        result.update(roofline_fields(timer, n_inst, rays_total / elapsed, mode, args.config))
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "c2":
         result["cpu_baseline"] = cpu_baseline()
     if rank == 0:
         print(json.dumps(result), flush=True)

@@ -40,6 +40,32 @@ PINNED = {
 }
 
 
+PART_LIMIT = 900 * 1024  # bytes per committed fixture file (kept under 1 MiB)
+
+
+def save_fixture(name, **arrays):
+    """Write <name>.npz; a fixture past PART_LIMIT goes into <name>.npz, <name>.part2.npz, ... with
+    disjoint keys in their given order (tests/helpers.py fixture_arrays reads them back as one)."""
+    import glob
+    import io
+    import zipfile
+    buf = io.BytesIO()
+    np.savez_compressed(buf, **arrays)
+    sizes = {i.filename[:-len(".npy")]: i.compress_size + 2 * len(i.filename) + 128
+             for i in zipfile.ZipFile(buf).infolist()}
+    parts, room = [], 0
+    for k in arrays:
+        if not parts or sizes[k] > room:
+            parts.append({})
+            room = PART_LIMIT
+        parts[-1][k] = arrays[k]
+        room -= sizes[k]
+    for old in glob.glob(os.path.join(OUT, name + ".part*.npz")):
+        os.remove(old)
+    for n, part in enumerate(parts, 1):
+        np.savez_compressed(os.path.join(OUT, name + (".npz" if n == 1 else f".part{n}.npz")), **part)
+
+
 def _ref_text(rel):
     """The text of a pinned reference source file (refuses a file whose hash differs)."""
     import hashlib
@@ -189,8 +215,8 @@ def render_case(fields, rend, name, *, seed, R, dh_sdf, dh_col, eval_mode, car, 
     # parameters are rebuilt from the seed by the tests; checksums pin that
     for (k, p) in params:
         put_param(rec, k, p)
-    np.savez_compressed(os.path.join(OUT, name + ".npz"),
-                        **{k: (v.numpy() if torch.is_tensor(v) else v) for k, v in rec.items()})
+    save_fixture(name,
+                 **{k: (v.numpy() if torch.is_tensor(v) else v) for k, v in rec.items()})
     print("wrote", name, sorted(rec)[:6], "...")
 
 
@@ -230,8 +256,8 @@ def pretrained_case(fields, rend, name="render_pretrained", seed=690, R=256):
     gen = torch.Generator().manual_seed(1234)
     for (k, p), gr in zip(params, grads):
         put_grad(rec, k, gr, False, gen)
-    np.savez_compressed(os.path.join(OUT, name + ".npz"),
-                        **{k: (v.numpy() if torch.is_tensor(v) else v) for k, v in rec.items()})
+    save_fixture(name,
+                 **{k: (v.numpy() if torch.is_tensor(v) else v) for k, v in rec.items()})
     print("wrote", name)
 
 
@@ -302,8 +328,8 @@ def seams_case(fields, rend):
     for (k, p), gr in zip(cparams, cg[:-2]):
         put_grad(rec, "colnet." + k, gr, False, gen)
         put_param(rec, "colnet." + k, p)
-    np.savez_compressed(os.path.join(OUT, "seams.npz"),
-                        **{k: (v.detach().numpy() if torch.is_tensor(v) else v) for k, v in rec.items()})
+    save_fixture("seams",
+                 **{k: (v.detach().numpy() if torch.is_tensor(v) else v) for k, v in rec.items()})
     print("wrote seams")
 
 
@@ -331,7 +357,7 @@ def motion_case(fields):
         rec[tag + "dt"] = np.float32(dt)
         rec[tag + "rel"] = torch.stack(rel).detach().numpy()
         rec[tag + "w2c"] = m.compute_w2c_mappings(rel).detach().numpy()
-    np.savez_compressed(os.path.join(OUT, "motion.npz"), **rec)
+    save_fixture("motion", **rec)
     print("wrote motion")
 
 
@@ -429,8 +455,8 @@ def trainer_case():
     rec["cl_rgb"], rec["cl_terms"] = rr, terms
     for k in ("loss", "loss_rgb", "l2_mean"):
         rec["cl_" + k] = d[k].detach()
-    np.savez_compressed(os.path.join(OUT, "trainer.npz"),
-                        **{k: (v.detach().numpy() if torch.is_tensor(v) else v) for k, v in rec.items()})
+    save_fixture("trainer",
+                 **{k: (v.detach().numpy() if torch.is_tensor(v) else v) for k, v in rec.items()})
     print("wrote trainer")
 
 
@@ -560,8 +586,8 @@ def stage1_case(fields):
             else:  # large motion-network gradients: 256 sampled entries + norm + sum
                 put_grad(rec, c + k, gr, k.startswith("out."), gen)
         print(f"stage1 {tag}: sdf {l_sdf.item():.6f} flow {l_flow.item():.6f} cons {float(l_cons):.6f}")
-    np.savez_compressed(os.path.join(OUT, "stage1.npz"),
-                        **{k: (v.detach().numpy() if torch.is_tensor(v) else v) for k, v in rec.items()})
+    save_fixture("stage1",
+                 **{k: (v.detach().numpy() if torch.is_tensor(v) else v) for k, v in rec.items()})
     print("wrote stage1")
 
 

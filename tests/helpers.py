@@ -18,9 +18,21 @@ REN_CFG = dict(n_samples=64, n_importance=64, n_outside=0, up_sample_steps=4, pe
                n_max_network_queries=64000, importance_sampling_start=0, naive_render=False)
 
 
+def fixture_arrays(name):
+    """The arrays of a golden fixture: tests/golden/<name>.npz and, where make_golden.py had to split
+    it to keep every committed file small, its further parts <name>.part<N>.npz (disjoint keys)."""
+    import glob
+    paths = [os.path.join(GOLDEN, name + ".npz")] + sorted(glob.glob(os.path.join(GOLDEN, name + ".part*.npz")))
+    out = {}
+    for p in paths:
+        with np.load(p) as f:
+            assert not set(f.files) & set(out), p
+            out.update({k: f[k] for k in f.files})
+    return out
+
+
 def fixture(name):
-    with np.load(os.path.join(GOLDEN, name + ".npz")) as f:
-        return {k: torch.from_numpy(f[k]) if f[k].ndim else torch.tensor(f[k]) for k in f.files}
+    return {k: torch.from_numpy(v) if v.ndim else torch.tensor(v) for k, v in fixture_arrays(name).items()}
 
 
 def build_modules(seed, dh_sdf=256, dh_col=256, var=0.3, device="cpu"):

@@ -5,22 +5,17 @@ train.py (467-517) and warp_pixel (235-244): losses and their gradients with res
 the renderer outputs the block reads, the motion network and the SDF network, for frames
 before / at / after the world camera and the last frame, reference intervals (1, 2, 3)
 and (1, 5, 10), with and without sdf_consistency_enable_pose_grad.  CPU only."""
-import os
-
-import numpy as np
 import pytest
 import torch
 
-from helpers import check_grad
+from helpers import check_grad, fixture_arrays
 from oracle import neus_oracle as O
 
-FX = os.path.join(os.path.dirname(__file__), "golden", "stage1.npz")
 CASES = ("before", "world", "after", "last", "iv1510", "posegrad_before", "posegrad_after")
 
 
 def _fixture():
-    d = np.load(FX)
-    return {k: torch.from_numpy(d[k]) for k in d.files}
+    return {k: torch.from_numpy(v) for k, v in fixture_arrays("stage1").items()}
 
 
 def _nets(fx):

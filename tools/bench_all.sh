@@ -17,7 +17,7 @@ for c in $CONFIGS; do
     *) args="--config $c";;
   esac
   echo "== $c $args" >&2
-  timeout -k 10 400 python3 -u $R/bench.py $args > $O/bench_$c.json 2> $O/bench_$c.err || { echo "bench $c failed rc=$?" >&2; tail -5 $O/bench_$c.err >&2; exit 1; }
+  timeout -k 10 400 python3 -u $R/bench.py --full $args > $O/bench_$c.json 2> $O/bench_$c.err || { echo "bench $c failed rc=$?" >&2; tail -5 $O/bench_$c.err >&2; exit 1; }
   unset COPENERF_FORCE_DIST
   python3 -c "import json,sys; d=json.loads(open('$O/bench_$c.json').read().strip().splitlines()[-1]); r=d['roofline']; print('$c', d['value'], d['ms_per_step'], r['bound'], r['achieved'], r['unit'], r['frac'])" >&2
 done

@@ -11,7 +11,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/pmc_$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --timer-steps 1 $*"
+B="python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --timer-steps 1 $*"
 timeout -k 10 120 rocprofv3 -L > $O/counters.txt 2>&1 || true
 # the library build these counters belong to (bench.py reads PMC traffic only for its own build)
 cp $R/cope-nerf_amd/copenerf/libcopenerf.so.stamp $O/lib_stamp.txt
