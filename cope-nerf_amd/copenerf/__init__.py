@@ -12,8 +12,9 @@ from .rays import PoseRetriever  # noqa: F401
 from .motion import MotionNetwork  # noqa: F401
 from .trainer import Trainer  # noqa: F401
 from .checkpoints import CheckpointIO  # noqa: F401
+from .mesh import write_ply  # noqa: F401
 from . import _lib  # noqa: F401
 
 __all__ = ["NeuSRenderer", "SDFNetwork", "RenderingNetwork", "SingleVarianceNetwork", "NeRF",
            "EdgePreservingSmoothnessLoss", "SmoothnessLoss", "PoseRetriever", "MotionNetwork", "Trainer",
-           "CheckpointIO"]
+           "CheckpointIO", "write_ply"]

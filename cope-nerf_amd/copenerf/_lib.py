@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libcopenerf.so"
 LIB_PATH = os.environ.get("COPENERF_LIB", os.path.join(_HERE, LIB_NAME))
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 c_f32p = ctypes.c_void_p  # device pointers are passed as integers
 c_i32 = ctypes.c_int32
@@ -151,6 +151,21 @@ class MlpDesc(ctypes.Structure):
     ]
 
 
+class SdfGridDesc(ctypes.Structure):
+    _fields_ = [
+        ("net", ctypes.POINTER(SdfNet)), ("nx", c_i32), ("ny", c_i32), ("nz", c_i32), ("lo", c_f32 * 3),
+        ("hi", c_f32 * 3), ("time_step", c_ptr), ("u", c_ptr), ("chunk_rows", c_i32),
+    ]
+
+
+class MeshDesc(ctypes.Structure):
+    _fields_ = [
+        ("nx", c_i32), ("ny", c_i32), ("nz", c_i32), ("u", c_ptr), ("threshold", c_f32), ("lo", c_f32 * 3),
+        ("hi", c_f32 * 3), ("vertices", c_ptr), ("max_vertices", c_i64), ("triangles", c_ptr),
+        ("max_triangles", c_i64), ("counts", c_ptr),
+    ]
+
+
 # name -> (restype, argtypes); mirrors include/copenerf.h one to one.
 SIGNATURES = {
     "cn_abi_version": (c_i32, []),
@@ -226,6 +241,13 @@ SIGNATURES = {
     "cn_mlp_bwd_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(MlpDesc)]),
     "cn_mlp_fwd": (c_i32, [ctypes.POINTER(MlpDesc), c_ptr, c_i64, c_ptr]),
     "cn_mlp_bwd": (c_i32, [ctypes.POINTER(MlpDesc), c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
+    "cn_grid_points": (c_i32, [c_i32, c_i32, c_i32, ctypes.POINTER(c_f32), ctypes.POINTER(c_f32), c_ptr, c_i64, c_i32,
+                               c_ptr, c_ptr]),
+    "cn_sdf_grid_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SdfGridDesc)]),
+    "cn_sdf_grid": (c_i32, [ctypes.POINTER(SdfGridDesc), c_ptr, c_i64, c_ptr]),
+    "cn_mesh_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32]),
+    "cn_mesh_count": (c_i32, [ctypes.POINTER(MeshDesc), c_ptr, c_i64, c_ptr]),
+    "cn_mesh_emit": (c_i32, [ctypes.POINTER(MeshDesc), c_ptr, c_i64, c_ptr]),
 }
 
 _lock = threading.Lock()

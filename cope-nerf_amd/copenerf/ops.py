@@ -1013,3 +1013,108 @@ def train_loss(color, gt, depth, normals, *, w_rgb=1.0, w_eik=0.1, w_edge=1.0, w
               _ptr(weights), float(gamma), _ptr(loss), _ptr(dcolor), _ptr(ddepth), _ptr(dn), 3, _ptr(nonfinite),
               _ptr(ws), ws.numel() * 8, _stream())
     return loss, dcolor, ddepth, dn
+
+
+# ---------------------------------------------------------------------------
+# Mesh extraction (ABI v16)
+def _box(lo, hi):
+    lo = [float(v) for v in (lo.tolist() if hasattr(lo, "tolist") else lo)]
+    hi = [float(v) for v in (hi.tolist() if hasattr(hi, "tolist") else hi)]
+    if len(lo) != 3 or len(hi) != 3:
+        raise RuntimeError("copenerf: lo / hi must have three entries")
+    return (_lib.c_f32 * 3)(*lo), (_lib.c_f32 * 3)(*hi)
+
+
+def grid_points(dims, lo, hi, t, m0=0, M=None, out=None):
+    """Rows (X[ix], Y[iy], Z[iz], t) of the linear indices [m0, m0 + M) of an nx x ny x nz grid, z fastest;
+    every axis is torch.linspace(lo, hi, n) -- cn_grid_points.  t: float or 1-element device tensor."""
+    nx, ny, nz = (int(n) for n in dims)
+    M = nx * ny * nz - m0 if M is None else int(M)
+    if out is None:
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError("grid_points: t must be a device tensor (ops.device_scalar) when out is not given")
+        out = torch.empty(max(M, 0), 4, device=t.device)
+    _need(out, "out")
+    if not out.is_contiguous() or out.shape[1] != 4 or out.shape[0] < M:
+        raise RuntimeError("grid_points: out must be a contiguous [M, 4] tensor")
+    t = device_scalar(t, out.device)
+    clo, chi = _box(lo, hi)
+    _lib.call("cn_grid_points", nx, ny, nz, clo, chi, _ptr(t), int(m0), M, _ptr(out), _stream())
+    return out
+
+
+def sdf_grid(net, dims, lo, hi, t, chunk_rows=0, out=None):
+    """u [nx, ny, nz] = +SDFNetwork.sdf on the grid of grid_points, evaluated in chunks of chunk_rows rows
+    (0: 2^20) without leaving the device -- cn_sdf_grid (net: sdf_net's descriptor).  The sign is the
+    network's: negative inside.  isosurface orients its triangles toward larger u, so no negation."""
+    nx, ny, nz = (int(n) for n in dims)
+    if not isinstance(t, torch.Tensor) and out is None:
+        raise RuntimeError("sdf_grid: t must be a device tensor (ops.device_scalar) when out is not given")
+    dev = out.device if out is not None else t.device
+    if out is None:
+        out = torch.empty(nx, ny, nz, device=dev)
+    _need(out, "out", ndim=3)
+    if not out.is_contiguous() or tuple(out.shape) != (nx, ny, nz) or out.dtype != torch.float32:
+        raise RuntimeError("sdf_grid: out must be a contiguous fp32 [nx, ny, nz] tensor")
+    t = device_scalar(t, dev)
+    d = _lib.SdfGridDesc()
+    d.net, d.nx, d.ny, d.nz, d.chunk_rows = ctypes.pointer(net), nx, ny, nz, int(chunk_rows)
+    d.lo, d.hi = _box(lo, hi)
+    d.time_step, d.u = _ptr(t), _ptr(out)
+    lib = _lib.load()
+    ws = torch.empty(max(int(lib.cn_sdf_grid_workspace_bytes(ctypes.byref(d))), 1), dtype=torch.uint8, device=dev)
+    _lib.check(lib.cn_sdf_grid(ctypes.byref(d), _ptr(ws), ws.numel(), _stream()), "cn_sdf_grid")
+    return out
+
+
+def _mesh_desc(u, threshold, lo, hi, counts):
+    _need(u, "u", ndim=3)
+    if u.dim() != 3 or not u.is_contiguous() or u.dtype != torch.float32:
+        raise RuntimeError("isosurface: u must be a contiguous fp32 [nx, ny, nz] tensor")
+    d = _lib.MeshDesc()
+    d.nx, d.ny, d.nz = u.shape
+    d.u, d.threshold, d.counts = _ptr(u), float(threshold), _ptr(counts)
+    d.lo, d.hi = _box(lo, hi)
+    return d
+
+
+def mesh_count(u, threshold, lo, hi):
+    """The count pass of isosurface -- cn_mesh_count: (descriptor, workspace, counts) with counts a device
+    int64 [2] = (vertices, triangles); the workspace keeps the edge masks and offsets mesh_emit reads."""
+    counts = torch.empty(2, dtype=torch.int64, device=u.device if u.is_cuda else None)
+    d = _mesh_desc(u, threshold, lo, hi, counts)
+    lib = _lib.load()
+    ws = torch.empty(max(int(lib.cn_mesh_workspace_bytes(d.nx, d.ny, d.nz)), 1), dtype=torch.uint8, device=u.device)
+    _lib.check(lib.cn_mesh_count(ctypes.byref(d), _ptr(ws), ws.numel(), _stream()), "cn_mesh_count")
+    return d, ws, counts
+
+
+def mesh_emit(d, ws, vertices, triangles, counts=None):
+    """The emit pass -- cn_mesh_emit into vertices fp32 [V, 3] / triangles int32 [T, 3] with mesh_count's
+    descriptor and workspace.  counts: the (V, T) read back from mesh_count, checked here against the
+    buffers (the kernel checks the device counts again and writes nothing into buffers that are too small)."""
+    _need(vertices, "vertices")
+    _need(triangles, "triangles")
+    if (vertices.dtype != torch.float32 or triangles.dtype != torch.int32 or not vertices.is_contiguous() or
+            not triangles.is_contiguous() or vertices.shape[1] != 3 or triangles.shape[1] != 3):
+        raise RuntimeError("mesh_emit: vertices fp32 [V, 3] and triangles int32 [T, 3], contiguous")
+    if counts is not None and (vertices.shape[0] < counts[0] or triangles.shape[0] < counts[1]):
+        raise RuntimeError(f"mesh_emit: buffers of {vertices.shape[0]} vertices / {triangles.shape[0]} triangles "
+                           f"for counts {tuple(counts)}")
+    d.vertices, d.max_vertices = _ptr(vertices) if vertices.shape[0] else None, vertices.shape[0]
+    d.triangles, d.max_triangles = _ptr(triangles) if triangles.shape[0] else None, triangles.shape[0]
+    _lib.call("cn_mesh_emit", ctypes.byref(d), _ptr(ws), ws.numel(), _stream())
+
+
+def isosurface(u, threshold, lo, hi):
+    """The isosurface u = threshold of a device volume u [nx, ny, nz] over the box lo .. hi as a welded triangle
+    mesh: (vertices fp32 [V, 3], triangles int32 [T, 3]), device tensors ((0, 3) when empty).  Marching
+    tetrahedra on the Kuhn split; vertex and triangle order are fixed by the grid (include/copenerf.h), triangle
+    normals point toward larger u.  Count pass, one 16-byte read-back, an exact allocation, emit pass."""
+    d, ws, counts = mesh_count(u, threshold, lo, hi)
+    V, T = (int(c) for c in counts.tolist())
+    vertices = torch.empty(V, 3, device=u.device)
+    triangles = torch.empty(T, 3, dtype=torch.int32, device=u.device)
+    if V or T:
+        mesh_emit(d, ws, vertices, triangles, (V, T))
+    return vertices, triangles

@@ -7,4 +7,5 @@ resolves to the HIP-backed classes, so train.py's `mdl.Trainer(...)`,
 528-532) run against this build.
 """
 from copenerf import (CheckpointIO, EdgePreservingSmoothnessLoss, MotionNetwork, NeRF, NeuSRenderer,  # noqa: F401
-                      PoseRetriever, RenderingNetwork, SDFNetwork, SingleVarianceNetwork, SmoothnessLoss, Trainer)
+                      PoseRetriever, RenderingNetwork, SDFNetwork, SingleVarianceNetwork, SmoothnessLoss, Trainer,
+                      write_ply)

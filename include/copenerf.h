@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CN_ABI_VERSION 15
+#define CN_ABI_VERSION 16
 
 typedef void* cn_stream_t; /* hipStream_t */
 
@@ -776,6 +776,83 @@ size_t cn_mlp_bwd_workspace_bytes(const cn_mlp_desc* d);
 int cn_mlp_fwd(const cn_mlp_desc* d, void* state, int64_t state_bytes, cn_stream_t stream);
 int cn_mlp_bwd(const cn_mlp_desc* d, const void* state, int64_t state_bytes, void* workspace,
                int64_t workspace_bytes, cn_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
+ * Mesh extraction (ABI v16): NeuSRenderer.extract_geometry (neus_renderer.py:10-37,
+ * 588-591) on the device: the grid points of a bounding box at one time value, the SDF
+ * volume over them, and the isosurface of a volume as a welded triangle mesh.  The
+ * reference's extract_fields queries 3-column points in 64^3 blocks with a host copy
+ * each and meshes with PyMCubes; here the points are (x, y, z, t) rows, the volume
+ * stays on the device and the mesher is marching tetrahedra on the six-tetrahedron
+ * Kuhn split (DESIGN.md "Mesh extraction").
+ *
+ * cn_grid_points: pts [M][4] (16-byte aligned) = rows (X[ix], Y[iy], Z[iz], t) of the
+ * linear indices [m0, m0 + M) of an nx x ny x nz grid in C order (z fastest: the
+ * reference's u[xi, yi, zi]).  Each axis is torch.linspace(lo, hi, n) by its fp32 rule:
+ * step = (hi - lo) / (n - 1); lo + i step for i < n / 2, hi - (n - 1 - i) step otherwise.
+ * lo, hi: HOST float [3] (read during the call); time_step: device scalar [1].
+ * ------------------------------------------------------------------------ */
+int cn_grid_points(int32_t nx, int32_t ny, int32_t nz, const float* lo, const float* hi,
+                   const float* time_step, int64_t m0, int32_t M, float* pts, cn_stream_t stream);
+
+/* u [nx][ny][nz] = +SDFNetwork.sdf at the grid points: cn_grid_points + cn_sdf_query over
+ * chunks of chunk_rows rows (0: 2^20) on the caller's stream, bitwise the same for every
+ * chunk_rows.  The sign is the network's (negative inside): cn_mesh_* orient triangles by
+ * the volume's values, so no negation is needed (the reference meshes -sdf).
+ * chunk_rows x 256 bytes must stay below 2^31 (the fused bf16x6 query's row bound):
+ * larger is CN_ERR_SHAPE before anything launches.  Workspace (256-byte aligned):
+ * cn_sdf_grid_workspace_bytes = chunk x 16 bytes rounded up to 256 (one chunk's points)
+ * + cn_sdf_query_workspace_bytes(net, chunk), chunk = min(chunk_rows or 2^20, nx ny nz). */
+typedef struct cn_sdf_grid_desc {
+    const cn_sdf_net* net;
+    int32_t nx, ny, nz;
+    float lo[3], hi[3];
+    const float* time_step;
+    float* u;
+    int32_t chunk_rows;
+} cn_sdf_grid_desc;
+size_t cn_sdf_grid_workspace_bytes(const cn_sdf_grid_desc* d);
+int cn_sdf_grid(const cn_sdf_grid_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+
+/* The isosurface u = threshold of a volume u [nx][ny][nz] (fp32, device).
+ *  - Cells in C order over (nx-1, ny-1, nz-1); tetrahedron k = 0..5 of a cell belongs to the
+ *    k-th permutation pi of (x, y, z) in lexicographic order, corners v0 = (0,0,0),
+ *    v1 = v0 + e_pi0, v2 = v1 + e_pi1, v3 = (1,1,1); bit i of its mask is u[vi] < threshold
+ *    (strict: a tie is outside).
+ *  - Every tetrahedron edge runs from a grid vertex p to p + d, d in {0,1}^3 \ {0}, owned by
+ *    p in slot dx + 2 dy + 4 dz - 1.  An edge whose ends differ in the mask bit carries one
+ *    mesh vertex; vertex ids ascend by (linear index of p, slot).  Position: p + s d in index
+ *    space, s = (threshold - u_p) / (u_{p+d} - u_p), then per axis
+ *    pos / (n - 1) * (hi - lo) + lo, all in fp32.
+ *  - Triangles: A = the inside corners if at most two, else the outside corners, B the
+ *    others, both ascending.  A = {i}: (E_ij, E_ik, E_il); A = {i,j}: (E_ik, E_il, E_jl),
+ *    (E_ik, E_jl, E_jk); second and third index swapped where the midpoint triangle's normal
+ *    points from the outside corners' centroid toward the inside corners': normals point
+ *    toward larger u, out of the surface for an SDF.  Order: (cell, k, triangle).
+ * cn_mesh_count writes counts = (V, T) (DEVICE int64 [2]) and leaves the edge masks and the
+ * scanned offsets in the workspace; cn_mesh_emit, with the same volume, descriptor and
+ * workspace, writes vertices [V][3] and triangles [T][3].  The host cannot see counts
+ * without synchronising, so cn_mesh_emit checks max_vertices / max_triangles against them on
+ * the device: with a buffer smaller than the counts it writes nothing at all.  Deterministic:
+ * no atomics, no waits between workgroups.
+ * Workspace (256-byte aligned), every piece rounded up to 256 bytes, N = nx ny nz,
+ * C = (nx-1)(ny-1)(nz-1): N (edge masks) + 4 N (vertex offsets) + C (triangle counts) + 4 C
+ * (triangle offsets) + 4 ceil(N / 1024) + 4 ceil(C / 1024) (the scans' tile totals).
+ * Any dim below 2, 7 N >= 2^31 or 12 C >= 2^31: CN_ERR_SHAPE (workspace_bytes: 0). */
+typedef struct cn_mesh_desc {
+    int32_t nx, ny, nz;
+    const float* u;
+    float threshold;
+    float lo[3], hi[3];
+    float* vertices;            /* [max_vertices][3] -- cn_mesh_emit */
+    int64_t max_vertices;
+    int32_t* triangles;         /* [max_triangles][3] -- cn_mesh_emit */
+    int64_t max_triangles;
+    int64_t* counts;            /* device [2]: V, T */
+} cn_mesh_desc;
+size_t cn_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int cn_mesh_count(const cn_mesh_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+int cn_mesh_emit(const cn_mesh_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
 
 #ifdef __cplusplus
 }
