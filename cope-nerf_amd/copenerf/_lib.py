@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libcopenerf.so"
 LIB_PATH = os.environ.get("COPENERF_LIB", os.path.join(_HERE, LIB_NAME))
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 c_f32p = ctypes.c_void_p  # device pointers are passed as integers
 c_i32 = ctypes.c_int32
@@ -248,6 +248,9 @@ SIGNATURES = {
     "cn_mesh_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32]),
     "cn_mesh_count": (c_i32, [ctypes.POINTER(MeshDesc), c_ptr, c_i64, c_ptr]),
     "cn_mesh_emit": (c_i32, [ctypes.POINTER(MeshDesc), c_ptr, c_i64, c_ptr]),
+    "cn_refine_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32]),
+    "cn_refine_warp": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                               c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
 }
 
 _lock = threading.Lock()

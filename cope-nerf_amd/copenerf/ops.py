@@ -1118,3 +1118,67 @@ def isosurface(u, threshold, lo, hi):
     if V or T:
         mesh_emit(d, ws, vertices, triangles, (V, T))
     return vertices, triangles
+
+
+# ---------------------------------------------------------------------------
+# Pose refinement (ABI v17)
+class _RefineWarp(torch.autograd.Function):
+    """cn_refine_warp: the forward launches the fused pass and keeps dpose = d sums[:, 0] / d pose; the
+    backward is g_sums[:, 0, None] * dpose for the poses alone (the valid counts carry no gradient)."""
+
+    @staticmethod
+    def forward(ctx, pose, images, depth, tgt, src, K, Kinv, want_warped):
+        N, _, H, W = images.shape
+        J = tgt.shape[0]
+        dev = images.device
+        sums = torch.empty(J, 2, device=dev, dtype=torch.float32)
+        dpose = torch.empty(J, 12, device=dev, dtype=torch.float32)
+        warped = torch.empty(J, 3, H, W, device=dev, dtype=torch.float32) if want_warped else None
+        lib = _lib.load()
+        need = int(lib.cn_refine_workspace_bytes(J, H, W))
+        if J and need == 0:
+            _lib.check(lib.cn_refine_warp(N, H, W, J, None, None, None, None, None, None, None, None, None, None,
+                                          None, 0, None), "cn_refine_warp")
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        p = pose.detach().reshape(J, 12).contiguous()
+        _lib.call("cn_refine_warp", N, H, W, J, _ptr(images), _ptr(depth), _ptr(tgt), _ptr(src), _ptr(p), _ptr(K),
+                  _ptr(Kinv), _ptr(sums), _ptr(dpose), _ptr(warped), _ptr(ws), ws.numel(),
+                  torch.cuda.current_stream(dev).cuda_stream)
+        ctx.save_for_backward(dpose)
+        ctx.pose_shape = pose.shape
+        if warped is None:
+            warped = sums.new_empty(0)
+        ctx.mark_non_differentiable(warped)
+        return sums, warped
+
+    @staticmethod
+    def backward(ctx, g_sums, _g_warped):
+        (dpose,) = ctx.saved_tensors
+        return ((g_sums[:, 0, None] * dpose).reshape(ctx.pose_shape),) + (None,) * 7
+
+
+def refine_warp(images, depth, tgt, src, pose, K, Kinv, want_warped=False):
+    """The photometric warp of pose refinement for J (target, source) jobs -- cn_refine_warp.
+    images fp32 [N, 3, H, W], depth fp32 [N, H, W] (contiguous), tgt / src int32 [J], pose [J, 3, 4] (or
+    [J, 12]; the only differentiable input), K / Kinv fp32 [J, 3, 3].  Returns (sums [J, 2], warped):
+    sums[:, 0] = the masked L1 sum, sums[:, 1] = the number of valid pixels (no gradient); warped
+    [J, 3, H, W] when want_warped, else None."""
+    for t, name in ((images, "images"), (depth, "depth"), (tgt, "tgt"), (src, "src"), (pose, "pose"), (K, "K"),
+                    (Kinv, "Kinv")):
+        _need(t, name, ndim=0)
+    J = tgt.shape[0]
+    if (images.dim() != 4 or images.shape[1] != 3 or images.dtype != torch.float32 or not images.is_contiguous()):
+        raise RuntimeError("refine_warp: images must be a contiguous fp32 [N, 3, H, W] tensor")
+    if (tuple(depth.shape) != (images.shape[0],) + tuple(images.shape[2:]) or depth.dtype != torch.float32 or
+            not depth.is_contiguous()):
+        raise RuntimeError("refine_warp: depth must be a contiguous fp32 [N, H, W] tensor of the images' size")
+    if tgt.dtype != torch.int32 or src.dtype != torch.int32 or tuple(src.shape) != (J,) or tgt.dim() != 1:
+        raise RuntimeError("refine_warp: tgt / src must be int32 [J] tensors")
+    if pose.numel() != 12 * J or pose.dtype != torch.float32:
+        raise RuntimeError("refine_warp: pose must be fp32 [J, 3, 4]")
+    for t, name in ((K, "K"), (Kinv, "Kinv")):
+        if tuple(t.shape) != (J, 3, 3) or t.dtype != torch.float32:
+            raise RuntimeError(f"refine_warp: {name} must be fp32 [J, 3, 3]")
+    sums, warped = _RefineWarp.apply(pose, images, depth, tgt.contiguous(), src.contiguous(), K.contiguous(),
+                                     Kinv.contiguous(), bool(want_warped))
+    return sums, (warped if want_warped else None)

@@ -188,3 +188,19 @@ class PoseRetriever(nn.Module):
         if self.init_c2w is not None:
             c2w = c2w @ self.init_c2w.index_select(0, idx)[0]
         return c2w
+
+    def poses_at(self, idx):
+        """forward() for every camera of an index tensor [B] at once -> [B, 4, 4]: the same Rodrigues
+        arithmetic batched over the gathered rows, a constant number of launches whatever B is (the
+        pose batch of pose refinement, pose_refinement.py:118, is B separate make_c2w chains)."""
+        r = self.r.index_select(0, idx)
+        t = self.t.index_select(0, idx)
+        z = torch.zeros_like(r[:, 0])
+        K = torch.stack([z, -r[:, 2], r[:, 1], r[:, 2], z, -r[:, 0], -r[:, 1], r[:, 0], z], -1).view(-1, 3, 3)
+        th = (r.norm(dim=-1) + 1e-15).view(-1, 1, 1)
+        I = torch.eye(3, dtype=r.dtype, device=r.device)
+        R = I + (torch.sin(th) / th) * K + ((1 - torch.cos(th)) / th ** 2) * (K @ K)
+        c2w = convert3x4_4x4(torch.cat([R, t.unsqueeze(-1)], -1))
+        if self.init_c2w is not None:
+            c2w = c2w @ self.init_c2w.index_select(0, idx)
+        return c2w

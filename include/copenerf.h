@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CN_ABI_VERSION 16
+#define CN_ABI_VERSION 17
 
 typedef void* cn_stream_t; /* hipStream_t */
 
@@ -853,6 +853,44 @@ typedef struct cn_mesh_desc {
 size_t cn_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
 int cn_mesh_count(const cn_mesh_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
 int cn_mesh_emit(const cn_mesh_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
+ * Pose refinement (ABI v17): compute_loss_and_warp_image
+ * (utils_poses/pose_refinement.py:34-61) for J (target, source) jobs over one image
+ * stack, with the pose gradient in the same pass -- the per-batch work of
+ * perform_pose_refinement (pose_refinement.py:104-128) in one launch and one
+ * fixed-order reduction instead of a dozen full-image torch ops each way and
+ * grid_sample's backward.
+ *   images [N][3][H][W] planar (the reference's imgs), depth [N][H][W];
+ *   tgt [J], src [J]: int32 frame indices (the depth used is depth[tgt[j]]); a job with
+ *     an index outside [0, N) reads nothing and gives zero sums;
+ *   pose [J][12]: row-major 3 x 4 [R | t], the target camera's frame to the source's;
+ *   K [J][9], Kinv [J][9]: row-major 3 x 3.
+ * Per pixel (row i, column c) of the target, all fp32 without contraction:
+ *   u = c / ((W-1)/2) - 1, v = i / ((H-1)/2) - 1              (pose_refinement.py:93-100)
+ *   X = Kinv (u d, v d, d), Y = R X + t, q = K Y, (u', v') = (q0, q1) / q2
+ *   valid = u' and v' in [-1, 1] (the only test, as pose_refinement.py:50-53)
+ *   warp  = the bilinear sample of images[src] at (u', v'), border padding,
+ *           align_corners=True (Trainer.warp_pixel, train.py:235-244)
+ *   sums [J][2]   = (sum over valid pixels and the 3 channels of |warp - target|,
+ *                    the number of valid pixels)
+ *   dpose [J][12] = d sums[j][0] / d pose[j] (16-byte aligned): sign(warp - target) with
+ *                   sign(0) = 0, the bilinear derivative zero where the coordinate is
+ *                   clamped (torch's border rule), no gradient through the mask
+ *   warped        : NULL, or [J][3][H][W] = warp at every pixel (the reference's
+ *                   second return value)
+ * Reduction: one partial per 64 x 16 pixel tile and job, summed over a job's tiles in
+ * a fixed order; no atomics.  Bitwise reproducible, and a job's results do not depend
+ * on the other jobs of the call.  The valid counts are exact (below 2^24 per frame).
+ * Frame base offsets are 64-bit; H, W >= 2 and 3 H W < 2^31, J <= 65535 (else
+ * CN_ERR_SHAPE; cn_refine_workspace_bytes: 0).  Workspace (256-byte aligned):
+ * ceil(W / 64) ceil(H / 16) J x 64 bytes, rounded up to 256.  J = 0: nothing is written.
+ * ------------------------------------------------------------------------ */
+size_t cn_refine_workspace_bytes(int32_t J, int32_t H, int32_t W);
+int cn_refine_warp(int32_t N, int32_t H, int32_t W, int32_t J, const float* images, const float* depth,
+                   const int32_t* tgt, const int32_t* src, const float* pose, const float* K,
+                   const float* Kinv, float* sums, float* dpose, float* warped, void* workspace,
+                   int64_t workspace_bytes, cn_stream_t stream);
 
 #ifdef __cplusplus
 }
