@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libcopenerf.so"
 LIB_PATH = os.environ.get("COPENERF_LIB", os.path.join(_HERE, LIB_NAME))
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 c_f32p = ctypes.c_void_p  # device pointers are passed as integers
 c_i32 = ctypes.c_int32
@@ -251,6 +251,12 @@ SIGNATURES = {
     "cn_refine_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32]),
     "cn_refine_warp": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
                                c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
+    "cn_image_metrics_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32, c_i32]),
+    "cn_image_metrics": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, ctypes.POINTER(c_f32), c_ptr, c_ptr, c_ptr,
+                                 c_i64, c_ptr]),
+    "cn_depth_errors_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32]),
+    "cn_depth_errors": (c_i32, [c_i32, c_i32, c_i32, c_ptr, c_i32, c_i32, c_ptr, c_ptr, c_f32, c_f32, c_i32, c_ptr,
+                                c_ptr, c_i64, c_ptr]),
 }
 
 _lock = threading.Lock()

@@ -1182,3 +1182,71 @@ def refine_warp(images, depth, tgt, src, pose, K, Kinv, want_warped=False):
     sums, warped = _RefineWarp.apply(pose, images, depth, tgt.contiguous(), src.contiguous(), K.contiguous(),
                                      Kinv.contiguous(), bool(want_warped))
     return sums, (warped if want_warped else None)
+
+
+# ---------------------------------------------------------------------------
+# Evaluation metrics (ABI v18)
+def ssim_taps():
+    """The 11 window weights by the reference's own expression (co3d_metric.py:49-51): exp in Python
+    doubles, to fp32, divided by the fp32 sum."""
+    from math import exp
+    g = torch.tensor([exp(-(x - 11 // 2) ** 2 / float(2 * 1.5 ** 2)) for x in range(11)], dtype=torch.float32)
+    return g / g.sum()
+
+
+_SSIM_TAPS_HOST = None  # the 11 taps as a host array, built on first use (cn_image_metrics copies them per call)
+
+
+def _ssim_taps_host():
+    global _SSIM_TAPS_HOST
+    if _SSIM_TAPS_HOST is None:
+        _SSIM_TAPS_HOST = (_lib.c_f32 * 11)(*ssim_taps().tolist())
+    return _SSIM_TAPS_HOST
+
+
+def _need_plane_stack(fn, t, name, ndim):
+    _need(t, name, ndim=0)
+    if t.dtype != torch.float32 or t.dim() != ndim or not t.is_contiguous():
+        raise RuntimeError(f"{fn}: {name} must be a contiguous fp32 {ndim}-D tensor (got {t.dtype}, shape "
+                           f"{tuple(t.shape)}, strides {t.stride()})")
+
+
+def image_metrics(pred, gt, want_map=False):
+    """cn_image_metrics on contiguous fp32 [N, C, H, W] device tensors.  Returns (out, ssim_map): out
+    [N, C, 2] = (mean squared error, mean SSIM) per image and channel; ssim_map [N, C, H, W] when want_map,
+    else None."""
+    _need_plane_stack("image_metrics", pred, "pred", 4)
+    _need_plane_stack("image_metrics", gt, "gt", 4)
+    if pred.shape != gt.shape or pred.device != gt.device:
+        raise RuntimeError(f"image_metrics: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must agree")
+    N, C, H, W = pred.shape
+    dev = pred.device
+    out = torch.empty(N, C, 2, device=dev, dtype=torch.float32)
+    smap = torch.empty(N, C, H, W, device=dev, dtype=torch.float32) if want_map else None
+    lib = _lib.load()
+    need = int(lib.cn_image_metrics_workspace_bytes(N, C, H, W))
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    _lib.call("cn_image_metrics", N, C, H, W, _ptr(pred), _ptr(gt), _ssim_taps_host(), _ptr(out), _ptr(smap), _ptr(ws), need,
+              torch.cuda.current_stream(dev).cuda_stream)
+    return out, smap
+
+
+def depth_errors(gt, pred, ratio, min_depth, max_depth, clamp):
+    """cn_depth_errors: gt fp32 [N, Hg, Wg], pred fp32 [N, Hp, Wp], ratio fp32 [N] (all on the device,
+    contiguous).  Returns fp32 [N, 8]: abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, the valid count."""
+    _need_plane_stack("depth_errors", gt, "gt", 3)
+    _need_plane_stack("depth_errors", pred, "pred", 3)
+    _need_plane_stack("depth_errors", ratio, "ratio", 1)
+    N, Hg, Wg = gt.shape
+    if pred.shape[0] != N or ratio.shape[0] != N or pred.device != gt.device or ratio.device != gt.device:
+        raise RuntimeError(f"depth_errors: gt {tuple(gt.shape)}, pred {tuple(pred.shape)} and ratio "
+                           f"{tuple(ratio.shape)} must hold the same number of images on one device")
+    dev = gt.device
+    out = torch.empty(N, 8, device=dev, dtype=torch.float32)
+    lib = _lib.load()
+    need = int(lib.cn_depth_errors_workspace_bytes(N, Hg, Wg))
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    _lib.call("cn_depth_errors", N, Hg, Wg, _ptr(gt), pred.shape[1], pred.shape[2], _ptr(pred), _ptr(ratio),
+              float(min_depth), float(max_depth), int(bool(clamp)), _ptr(out), _ptr(ws), need,
+              torch.cuda.current_stream(dev).cuda_stream)
+    return out

@@ -184,6 +184,11 @@ class Trainer(object):
             self._nonfinite.zero_()
             raise AssertionError("Nan loss found")
 
+    def compute_depth_errors(self, gt_depth_map, pred_depth_map, min_depth=0.1, max_depth=80.0):
+        """training.py:126-154 on the device (metrics.compute_depth_errors)."""
+        from .metrics import compute_depth_errors
+        return compute_depth_errors(gt_depth_map, pred_depth_map, min_depth, max_depth)
+
     def backpropagation(self, loss_dict, train_motion_network):
         """training.py:552-558."""
         self.optimizer.zero_grad()

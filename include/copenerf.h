@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CN_ABI_VERSION 17
+#define CN_ABI_VERSION 18
 
 typedef void* cn_stream_t; /* hipStream_t */
 
@@ -891,6 +891,63 @@ int cn_refine_warp(int32_t N, int32_t H, int32_t W, int32_t J, const float* imag
                    const int32_t* tgt, const int32_t* src, const float* pose, const float* K,
                    const float* Kinv, float* sums, float* dpose, float* warped, void* workspace,
                    int64_t workspace_bytes, cn_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
+ * Evaluation metrics (ABI v18).
+ *
+ * cn_image_metrics: co3d_metric.py's psnr (lines 14-16) and ssim / _ssim (lines 18-48)
+ * for N x C (image, channel) planes in one fused pass: the reference runs five depthwise
+ * 11 x 11 convolutions and about fifteen full-image elementwise launches per pair
+ * (eval.py:190-221, after copying the rendered maps to the host and back).
+ *   pred, gt [N][C][H][W] contiguous fp32;
+ *   taps: HOST pointer to the 11 fp32 window weights (co3d_metric.py:49-51, built by the
+ *     caller; the library derives nothing).  Only window 11 exists.
+ *   out [N][C][2]  = (mean of (pred - gt)^2, mean of the SSIM map) per image and channel
+ *     (eval.py:204 calls psnr on an unbatched [3, H, W] tensor, so the reference's PSNR
+ *     is the mean of three per-channel PSNRs: the caller needs the channels apart);
+ *   ssim_map: NULL, or [N][C][H][W] = the SSIM map.
+ * Semantics, all fp32 without contraction (co3d_metric.py:28-43): the window applied to
+ * x, y, x x, y y, x y with zero padding of 5 on every side (separably: along x, then
+ * along y, taps in ascending order); sigma = E[.] - mu^2; C1 = 0.01^2, C2 = 0.03^2;
+ *   ssim = (2 mu1 mu2 + C1)(2 sigma12 + C2) / ((mu1^2 + mu2^2 + C1)(sigma1 + sigma2 + C2)),
+ * no clamping.  An image smaller than the window is legal.  Identical inputs give a map
+ * of exactly 1 and a squared error of exactly 0.
+ * Reduction: one fp32 partial per 64 x 16 tile and plane (lanes, then waves, in a fixed
+ * order); a second kernel sums a plane's tiles in a fixed order in double, divides by
+ * H W and rounds once.  No atomics: bitwise reproducible, and a plane's result does not
+ * depend on the rest of the batch.  Plane base offsets are 64-bit.
+ * C, H or W < 1, N < 0, N C > 65535, H W >= 2^31, 2^24 or more tiles per plane (more
+ * workgroups than the grid holds) or a workspace that is too small:
+ * CN_ERR_SHAPE (cn_image_metrics_workspace_bytes: 0).  N = 0: nothing is written, 0.
+ * Workspace (256-byte aligned): N C ceil(W / 64) ceil(H / 16) x 8 bytes, rounded up to 256.
+ *
+ * cn_depth_errors: Evaluator.depth_eval's per-image work (eval.py:233-241) and
+ * Trainer.compute_depth_errors (train.py:180-193; model/training.py:126-154 is the same
+ * without the clamp).  For each of N images, every ground-truth pixel (y, x) with
+ * min_depth <= gt <= max_depth takes
+ *   p = pred[y Hp / Hg][x Wp / Wg] * ratio[n]      (integer division; ratio: DEVICE [N]),
+ * clamped to [min_depth, max_depth] when clamp != 0, and with d = gt - p,
+ * thresh = max(gt / p, p / gt):
+ *   out [N][8] = mean |d| / gt, mean d^2 / gt, sqrt(mean d^2), sqrt(mean (log gt - log p)^2),
+ *                mean(thresh < 1.25), mean(thresh < 1.25^2), mean(thresh < 1.25^3), count.
+ * No valid pixel: seven NaN and count 0.  The counts are summed exactly (per-workgroup
+ * integers, then double) and rounded to fp32 once, like the other sums.
+ * The nearest-neighbour rule is floor(dst * src_size / dst_size); the reference uses
+ * cv2.resize(INTER_NEAREST), which was not available to compare against: the rule is
+ * unambiguous (and tested) for equal sizes and integer ratios only.
+ * The median ratio (eval.py:237) is the caller's: copenerf.metrics computes it on the device.
+ * N < 0, N > 65535, any size < 1, Hg Wg or Hp Wp >= 2^31, or a workspace that is too small:
+ * CN_ERR_SHAPE.  Workspace (256-byte aligned): N ceil(Hg Wg / 2048) x 32 bytes, rounded
+ * up to 256.
+ * ------------------------------------------------------------------------ */
+size_t cn_image_metrics_workspace_bytes(int32_t N, int32_t C, int32_t H, int32_t W);
+int cn_image_metrics(int32_t N, int32_t C, int32_t H, int32_t W, const float* pred, const float* gt,
+                     const float* taps, float* out, float* ssim_map, void* workspace,
+                     int64_t workspace_bytes, cn_stream_t stream);
+size_t cn_depth_errors_workspace_bytes(int32_t N, int32_t Hg, int32_t Wg);
+int cn_depth_errors(int32_t N, int32_t Hg, int32_t Wg, const float* gt, int32_t Hp, int32_t Wp,
+                    const float* pred, const float* ratio, float min_depth, float max_depth, int32_t clamp,
+                    float* out, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
 
 #ifdef __cplusplus
 }
