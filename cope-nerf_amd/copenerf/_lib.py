@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libcopenerf.so"
 LIB_PATH = os.environ.get("COPENERF_LIB", os.path.join(_HERE, LIB_NAME))
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 c_f32p = ctypes.c_void_p  # device pointers are passed as integers
 c_i32 = ctypes.c_int32
@@ -257,6 +257,12 @@ SIGNATURES = {
     "cn_depth_errors_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32]),
     "cn_depth_errors": (c_i32, [c_i32, c_i32, c_i32, c_ptr, c_i32, c_i32, c_ptr, c_ptr, c_f32, c_f32, c_i32, c_ptr,
                                 c_ptr, c_i64, c_ptr]),
+    "cn_ray_visuals_workspace_bytes": (ctypes.c_size_t, [c_i32]),
+    "cn_ray_visuals": (c_i32, [c_i32, c_i32, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i32, c_ptr, c_ptr, c_f32, c_ptr,
+                               c_ptr, ctypes.POINTER(c_f32), c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
+    "cn_visual_images_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32]),
+    "cn_visual_images": (c_i32, [c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                 c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
 }
 
 _lock = threading.Lock()

@@ -34,8 +34,19 @@ def arange_pixels(h, w, device="cpu"):
 
 @torch.no_grad()
 def render_image(renderer, camera_mat, world_mat, scale_mat, resolution, time_step, *, depth_range=(0.01, 5.0),
-                 cos_anneal_ratio=1.0, it=0, chunk=65536, motion=None, next_time_step=None, nb_sample_timestep=10):
-    """Render a full image; returns a dict of device tensors shaped [h, w, ·]."""
+                 cos_anneal_ratio=1.0, it=0, chunk=65536, motion=None, next_time_step=None, nb_sample_timestep=10,
+                 motion_time_step=None, ray_visuals="torch"):
+    """Render a full image; returns a dict of device tensors shaped [h, w, ·].
+
+    The flow integrates the motion network's velocities from motion_time_step (default: time_step, the time
+    the scene is queried at; render_visdata queries at another camera's time, training.py:168-171, 222) to
+    next_time_step in nb_sample_timestep Euler steps.  ray_visuals selects the per-chunk tail: "torch" (the
+    default) composes it from torch ops, "fused" runs it in one pass over the samples (cn_ray_visuals);
+    rgb, depth and weighted_z do not depend on the choice, normal, depth_highest_weight under a world
+    matrix and flow agree to rounding."""
+    if ray_visuals not in ("torch", "fused"):
+        raise ValueError("ray_visuals must be 'torch' or 'fused'")
+    fused = ray_visuals == "fused"
     h, w = resolution
     dev = camera_mat.device
     _, pixels = arange_pixels(h, w, device=dev)
@@ -43,9 +54,16 @@ def render_image(renderer, camera_mat, world_mat, scale_mat, resolution, time_st
     identity = torch.equal(world_mat, torch.eye(4, device=dev))
     flows = motion is not None and next_time_step is not None
     if flows:  # velocities along [t, t_next) (training.py:197-201)
-        steps = torch.linspace(float(t), float(next_time_step), nb_sample_timestep + 1, device=dev)[:-1]
+        t0 = float(t) if motion_time_step is None else float(motion_time_step)
+        steps = torch.linspace(t0, float(next_time_step), nb_sample_timestep + 1, device=dev)[:-1]
         omegas, vels = motion(steps.view(-1, 1))
-        dt = (float(next_time_step) - float(t)) / nb_sample_timestep
+        dt = (float(next_time_step) - t0) / nb_sample_timestep
+        if fused:
+            omegas, vels = omegas.float().contiguous(), vels.float().contiguous()
+            proj = (scale_mat[:3, :3] @ camera_mat[:3, :3]).float().contiguous()
+    if fused:
+        from .visualize import ray_visuals as fused_tail
+        world = None if identity else world_mat.float().contiguous()
     acc = {k: [] for k in ("rgb", "depth", "weighted_z", "normal", "depth_max_w", "flow")}
     for i in range(0, pixels.shape[0], chunk):
         pix = pixels[i:i + chunk]
@@ -57,6 +75,14 @@ def render_image(renderer, camera_mat, world_mat, scale_mat, resolution, time_st
         acc["rgb"].append(out["color_fine"])
         acc["depth"].append(out["depth_pred"])
         acc["weighted_z"].append(out["weighted_z_vals"])
+        if fused:
+            kw = dict(omega=omegas, vel=vels, dt=dt, proj=proj, pix=pix, flow_hw=(h, w)) if flows else {}
+            vis = fused_tail(pts, out["normals"], wts, world_mat=world, **kw)
+            acc["normal"].append(vis["normal"])
+            acc["depth_max_w"].append(vis["depth_max_w"])
+            if flows:
+                acc["flow"].append(vis["flow"])  # in pixels already
+            continue
         normal = (out["normals"] * wts[:, :, None]).sum(1)
         amax = wts.argmax(1)
         p_max = pts[torch.arange(pts.shape[0], device=dev), amax]
@@ -81,7 +107,9 @@ def render_image(renderer, camera_mat, world_mat, scale_mat, resolution, time_st
         "normal": torch.cat(acc["normal"]).view(h, w, 3),
         "depth_highest_weight": torch.cat(acc["depth_max_w"]).view(h, w),
     }
-    if flows:
+    if flows and fused:
+        res["flow"] = torch.cat(acc["flow"]).view(h, w, 2)
+    elif flows:
         f = torch.cat(acc["flow"]).view(h, w, 2).clone()
         f[..., 0] *= w / 2
         f[..., 1] *= h / 2

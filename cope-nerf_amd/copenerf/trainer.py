@@ -18,9 +18,11 @@ Differences, by design:
   * compute_loss checks for NaN like training.py:532-533 (`nan_check="sync"`,
     the default: AssertionError at once) or sets a device flag without a host
     sync (`nan_check="deferred"`, for captured steps; `check_finite()` raises).
-  * render_visdata / the visualisation helpers (training.py:157-374: cv2,
-    imageio, matplotlib output) are outside the hot path; copenerf.inference
-    renders full images on the device.
+  * render_visdata (training.py:157-374) renders on the device
+    (copenerf.visualize: inference.render_image with the fused per-ray pass,
+    the image arithmetic in cn_visual_images) and writes its PNG files with
+    PIL instead of imageio; the arrays it returns and the files' names are
+    the reference's.
 """
 from __future__ import annotations
 
@@ -188,6 +190,18 @@ class Trainer(object):
         """training.py:126-154 on the device (metrics.compute_depth_errors)."""
         from .metrics import compute_depth_errors
         return compute_depth_errors(gt_depth_map, pred_depth_map, min_depth, max_depth)
+
+    def render_visdata(self, data, world_mat, query_cam_idx, resolution, it, anneal_end, out_render_path=None, idx=None,
+                       render_only=False):
+        """training.py:157-374 (copenerf.visualize.render_visdata with the trainer's state): renders image
+        `idx`, returns {'render_image', 'render_depth', 'render_normal'} and, unless render_only, writes the
+        five images, updates self.depth_range[1] and logs the depth statistics and errors."""
+        from .visualize import render_visdata
+        crop = self.cfg_all.get("dataloading", {}).get("crop_size", 0)
+        return render_visdata(self.renderer, data, world_mat, query_cam_idx, resolution, it, anneal_end,
+                              total_nb_images=self.total_nb_images, nb_sample_timestep=self.cfg["nb_sample_timestep"],
+                              depth_range=self.depth_range, cfg=self.cfg, out_render_path=out_render_path, idx=idx,
+                              render_only=render_only, gt_depths=self.gt_depths, logger=self.logger, crop_size=crop)
 
     def backpropagation(self, loss_dict, train_motion_network):
         """training.py:552-558."""

@@ -8,4 +8,4 @@ resolves to the HIP-backed classes, so train.py's `mdl.Trainer(...)`,
 """
 from copenerf import (CheckpointIO, EdgePreservingSmoothnessLoss, MotionNetwork, NeRF, NeuSRenderer,  # noqa: F401
                       PoseRetriever, RenderingNetwork, SDFNetwork, SingleVarianceNetwork, SmoothnessLoss, Trainer,
-                      compute_pose_error, evaluate, write_ply)
+                      compute_pose_error, evaluate, render_train_views, render_visdata, write_ply)

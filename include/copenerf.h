@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CN_ABI_VERSION 18
+#define CN_ABI_VERSION 19
 
 typedef void* cn_stream_t; /* hipStream_t */
 
@@ -948,6 +948,90 @@ size_t cn_depth_errors_workspace_bytes(int32_t N, int32_t Hg, int32_t Wg);
 int cn_depth_errors(int32_t N, int32_t Hg, int32_t Wg, const float* gt, int32_t Hp, int32_t Wp,
                     const float* pred, const float* ratio, float min_depth, float max_depth, int32_t clamp,
                     float* out, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
+ * Visualisation renders (ABI v19): Trainer.render_visdata (model/training.py:157-374).
+ *
+ * cn_ray_visuals: the per-ray tail of the render loop (training.py:236-281) for R rays of
+ * S samples in one read of the samples (28 bytes each), instead of a clone of the points,
+ * K passes of cross / add / mul over [R S, 3], weighted sums, an argmax and a gather.
+ *   pts [R S][ld_p], normals [R S][ld_n]: columns 0..2 are used (ld in elements, >= 3;
+ *     when both have rows of a multiple of 4 floats on a 16-byte boundary, a row is one
+ *     16-byte load: its fourth float is read and must lie inside the caller's buffer);
+ *   weights [R][S] contiguous;
+ *   world_mat: DEVICE [4][4] row-major, or NULL for the identity;
+ *   omega [K][3], vel [K][3]: DEVICE, the K Euler steps' angular and linear velocities;
+ *     dt: the HOST step length;  0 <= K <= 1024;
+ *   proj: DEVICE [3][3] = scale_mat[:3,:3] @ camera_mat[:3,:3] (the caller's product);
+ *   pix [R][2]: the rays' normalised pixel coordinates;
+ *   flow_scale: HOST [2] = (w / 2, h / 2).
+ * Outputs, each may be NULL (an input only a NULL output reads may be NULL as well):
+ *   normal [R][3]   = sum_s w n, multiplied by world_mat[:3,:3] when world_mat is given
+ *                     (training.py:255-260);
+ *   depth_max_w [R] = -(world_mat (p*, 1))[2] with p* the sample of the largest weight,
+ *                     the lowest index among equal weights (torch.max, training.py:236-243);
+ *                     with a NULL world_mat exactly -p*[2].  All weights NaN: sample 0;
+ *   flow [R][2]     = ((q.xy / q.z) - pix) * flow_scale, q = proj P, P = sum_s w_s p_s^(K),
+ *                     p^(k+1) = p^(k) + dt (omega_k x p^(k) + vel_k)   (training.py:269-281,
+ *                     299-300).  IEEE results propagate when q.z = 0.
+ * Every Euler step is affine in p, so the K steps compose into one map p -> A p + b and
+ * sum_s w (A p + b) = A sum_s w p + b sum_s w: a one-wavefront kernel composes (A | b)
+ * from omega and vel on the device (no host synchronisation) into the workspace, and the
+ * main kernel forms sum w p, sum w, sum w n and the arg-max per ray -- one wavefront per
+ * ray, lane l taking samples l, l + 64, ... in ascending order, the lanes combined in a
+ * fixed order.  A ray's results depend on that ray alone and are bitwise reproducible.
+ * The sums are fp32 (fused multiply-adds); they differ from the reference's per-sample
+ * composition by rounding only.  Row offsets are 64-bit.
+ * R < 0, S < 1, K outside [0, 1024], ld_p or ld_n < 3, a workspace that is too small:
+ * CN_ERR_SHAPE.  flow with K = 0, or without proj / pix / flow_scale / omega / vel; NULL
+ * weights; NULL pts with flow or depth_max_w; NULL normals with normal: CN_ERR_ARG.
+ * Everything is checked before the first launch.  R = 0: nothing is written, 0.
+ * Workspace (256-byte aligned, needed for a flow only): cn_ray_visuals_workspace_bytes(K)
+ * = 256 for 1 <= K <= 1024, else 0.
+ *
+ * cn_visual_images: the per-image arithmetic of training.py:292-318, 343-345 for one
+ * H x W render: a statistics pass (one partial per 2048 pixels, then one wavefront over
+ * the partials in a fixed order), then one pass that writes the images.  No atomics; min
+ * and max do not depend on the order, so the statistics are exact.
+ *   rgb [HW][3], depth [HW], depth_max_w [HW], weighted_z [HW], normal [HW][3],
+ *   flow [HW][2] (may be NULL): contiguous fp32.
+ *   stats [5] fp32 (DEVICE) = min weighted_z, max weighted_z, max 1 / depth,
+ *     max 1 / depth_max_w, max |flow| = sqrt(fx fx + fy fy) (0 without a flow).  A NaN
+ *     input gives a NaN statistic (numpy's min / max).  stats may be NULL when no
+ *     disparity or flow image is asked for; with stats, depth, depth_max_w and
+ *     weighted_z are required.
+ *   uint8 images, each may be NULL (an image needs its input); trunc() toward zero, NaN
+ *   gives 0, every value clamped to [0, 255]; fp32, each operation rounded, none fused:
+ *     img [H][W][3]        = trunc(rgb * 255)                         (training.py:293);
+ *     disparity [H][W]     = trunc(((1 / depth) / stats[2]) * 255)    (training.py:309-310, 329);
+ *     disparity_hw [H][W]  = trunc(((1 / depth_max_w) / stats[3]) * 255)   (311-312, 330);
+ *       the contract is positive depths;
+ *     normal_img [H][W][3] = trunc(normal * 128 + 128)                (training.py:314-318);
+ *     flow_img [H][W][3]   = torchvision.utils.flow_to_image (training.py:302), that is:
+ *       the wheel has 55 rows from the segments RY 15, YG 6, GC 4, CB 11, BM 13, MR 6 with
+ *       the ramps floor(255 i / n):  RY (255, r, 0), YG (255 - r, 255, 0), GC (0, 255, r),
+ *       CB (0, 255 - r, 255), BM (r, 0, 255), MR (255, 0, 255 - r);
+ *       u = flow / (stats[4] + FLT_EPSILON), norm = |u|, a = atan2(-u.y, -u.x) / pi,
+ *       fk = (a + 1) / 2 * 54, k0 = floor(fk), k1 = (k0 + 1) mod 55, f = fk - k0;
+ *       per channel col = (1 - f) wheel[k0] / 255 + f wheel[k1] / 255,
+ *       col = 1 - norm (1 - col), pixel = floor(255 col).
+ *       A zero flow field gives an all-white image exactly.
+ * H or W < 1, H W >= 2^31, a workspace that is too small: CN_ERR_SHAPE
+ * (cn_visual_images_workspace_bytes: 0).  NULL stats with a disparity or flow image, an
+ * image without its input: CN_ERR_ARG.  Workspace (256-byte aligned, needed with stats):
+ * ceil(H W / 2048) x 32 bytes, rounded up to 256.
+ * ------------------------------------------------------------------------ */
+size_t cn_ray_visuals_workspace_bytes(int32_t K);
+int cn_ray_visuals(int32_t R, int32_t S, const float* pts, int64_t ld_p, const float* normals, int64_t ld_n,
+                   const float* weights, const float* world_mat, int32_t K, const float* omega,
+                   const float* vel, float dt, const float* proj, const float* pix, const float* flow_scale,
+                   float* normal, float* depth_max_w, float* flow, void* workspace, int64_t workspace_bytes,
+                   cn_stream_t stream);
+size_t cn_visual_images_workspace_bytes(int32_t H, int32_t W);
+int cn_visual_images(int32_t H, int32_t W, const float* rgb, const float* depth, const float* depth_max_w,
+                     const float* weighted_z, const float* normal, const float* flow, float* stats,
+                     uint8_t* img, uint8_t* disparity, uint8_t* disparity_hw, uint8_t* normal_img,
+                     uint8_t* flow_img, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
 
 #ifdef __cplusplus
 }
