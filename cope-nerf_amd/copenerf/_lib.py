@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libcopenerf.so"
 LIB_PATH = os.environ.get("COPENERF_LIB", os.path.join(_HERE, LIB_NAME))
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 c_f32p = ctypes.c_void_p  # device pointers are passed as integers
 c_i32 = ctypes.c_int32
@@ -166,6 +166,17 @@ class MeshDesc(ctypes.Structure):
     ]
 
 
+LPIPS_CONVS, LPIPS_TAPS = 13, 5
+
+
+class LpipsDesc(ctypes.Structure):
+    _fields_ = [
+        ("pred", c_ptr), ("gt", c_ptr), ("H", c_i32), ("W", c_i32), ("weights", c_ptr * LPIPS_CONVS),
+        ("bias", c_ptr * LPIPS_CONVS), ("lin", c_ptr * LPIPS_TAPS), ("mfma_dtype", c_i32), ("band_rows", c_i32),
+        ("out", c_ptr),
+    ]
+
+
 # name -> (restype, argtypes); mirrors include/copenerf.h one to one.
 SIGNATURES = {
     "cn_abi_version": (c_i32, []),
@@ -263,6 +274,11 @@ SIGNATURES = {
     "cn_visual_images_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32]),
     "cn_visual_images": (c_i32, [c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
                                  c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
+    "cn_lpips_patches": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_i32, c_i32, c_i32, c_ptr, c_ptr]),
+    "cn_lpips_head_workspace_bytes": (ctypes.c_size_t, [c_i64]),
+    "cn_lpips_head": (c_i32, [c_i32, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
+    "cn_lpips_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32, c_i32]),
+    "cn_lpips": (c_i32, [ctypes.POINTER(LpipsDesc), c_ptr, c_i64, c_ptr]),
 }
 
 _lock = threading.Lock()

@@ -2,6 +2,8 @@
 
   image metrics   psnr / ssim with co3d_metric.py's signatures on the fused device pass (cn_image_metrics),
                   image_metrics = Evaluator.image_eval (eval.py:190-221);
+  LPIPS           co3d_metric.lpips(net_type="vgg") on the device (cn_lpips) from the user's two weight files:
+                  load_lpips_weights, LPIPS;
   depth metrics   depth_metrics = Evaluator.depth_eval (eval.py:223-244) and compute_depth_errors
                   (model/training.py:126-154) on cn_depth_errors, the median ratio computed on the device;
   pose metrics    align_ate_c2b_use_a2b, compute_ATE, compute_rpe, compute_pose_error (train.py:169-178,
@@ -11,8 +13,9 @@
                   above and merge the dictionaries in eval.py:264-267's order; write_results writes
                   results.txt (eval.py:268-270).
 
-LPIPS needs network weights that are fetched on first use; they are not part of this build.  Pass
-lpips_fn(pred, gt) (both [3, H, W]) to have the "LPIPS" key; without it the key is absent.
+LPIPS needs network weights that are not part of this build and are never fetched: the user passes the two
+files (a torchvision VGG16 state dict and LPIPS v0.1's vgg.pth) to load_lpips_weights, and LPIPS(weights) is
+the lpips_fn(pred, gt) (both [3, H, W]) that gives the "LPIPS" key; without an lpips_fn the key is absent.
 
 The image and depth kernels have no CPU path: tensors must live on the device.  Host arrays (numpy, as the
 reference's depth loaders give) are uploaded.
@@ -22,7 +25,9 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import ops
+import ctypes
+
+from . import _lib, ops
 
 DEPTH_KEYS = ("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3")
 
@@ -104,6 +109,129 @@ def image_metrics(pred, gt, lpips_fn=None):
     if lpips_fn is not None:
         res["LPIPS"] = float(torch.cat(lp).mean())
     return res
+
+
+# ---------------------------------------------------------------------------
+# LPIPS (VGG16 features, the v0.1 linear heads)
+LPIPS_WIDTHS = (64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512)
+LPIPS_TAP_CHANNELS = (64, 128, 256, 512, 512)
+_VGG_FEATURES = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)  # torchvision's features.N of the 13 convolutions
+
+
+def _state_dict(path):
+    try:
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+    except Exception as e:
+        raise ValueError(f"load_lpips_weights: {path} is not a weights-only state dict ({type(e).__name__}: {e})") from e
+    if not isinstance(sd, dict):
+        raise ValueError(f"load_lpips_weights: {path} holds a {type(sd).__name__}, not a state dict")
+    return sd
+
+
+def _entry(sd, path, key, shape):
+    t = sd.get(key)
+    if not torch.is_tensor(t):
+        raise KeyError(f"load_lpips_weights: {path} has no tensor {key!r}")
+    if tuple(t.shape) != shape:
+        raise ValueError(f"load_lpips_weights: {path}: {key!r} is {tuple(t.shape)}, expected {shape}")
+    return t.detach().float()
+
+
+def lpips_conv_matrix(w, kpad=None):
+    """A convolution weight [Cout, Cin, 3, 3] as cn_lpips' GEMM operand [Cout, Kpad]: column
+    (dy 3 + dx) Cin + c, zero columns up to kpad (default 9 Cin rounded up to 32)."""
+    cout, cin = w.shape[:2]
+    k = 9 * cin
+    kpad = ops.rup(k, 32) if kpad is None else kpad
+    out = torch.zeros(cout, kpad, dtype=w.dtype, device=w.device)
+    out[:, :k] = w.permute(0, 2, 3, 1).reshape(cout, k)
+    return out
+
+
+def load_lpips_weights(vgg_path, lin_path):
+    """The LPIPS network from the user's two files (both loaded with weights_only=True; nothing is fetched):
+      vgg_path  torchvision's VGG16 state dict: features.{0, 2, 5, ..., 28}.weight [Cout, Cin, 3, 3] / .bias;
+      lin_path  LPIPS v0.1's vgg.pth: lin{0..4}.model.1.weight [1, C, 1, 1].
+    Every shape is checked; a missing or mis-shaped entry raises with its key.  Returns host tensors:
+    {"conv": 13 x [Cout, Kpad] (lpips_conv_matrix), "bias": 13 x [Cout], "lin": 5 x [C]}."""
+    vgg, lin = _state_dict(vgg_path), _state_dict(lin_path)
+    conv, bias, cin = [], [], 3
+    for i, cout in zip(_VGG_FEATURES, LPIPS_WIDTHS):
+        conv.append(lpips_conv_matrix(_entry(vgg, vgg_path, f"features.{i}.weight", (cout, cin, 3, 3))))
+        bias.append(_entry(vgg, vgg_path, f"features.{i}.bias", (cout,)).contiguous())
+        cin = cout
+    lins = [_entry(lin, lin_path, f"lin{t}.model.1.weight", (1, c, 1, 1)).reshape(c).contiguous()
+            for t, c in enumerate(LPIPS_TAP_CHANNELS)]
+    return {"conv": conv, "bias": bias, "lin": lins}
+
+
+class LPIPS:
+    """co3d_metric.lpips(pred, gt, net_type="vgg") on the device (cn_lpips): images in [0, 1], no rescale.
+    weights: load_lpips_weights' dict.  mode: the convolutions' MFMA format, "bf16x6" (fp32 results from bf16
+    terms, the default), "bf16" or "fp32".  The weights are packed once; a workspace is kept per image size.
+    Usable directly as image_metrics' / evaluate's lpips_fn.  There is no CPU path."""
+
+    def __init__(self, weights, mode="bf16x6", device=None, band_rows=0):
+        if mode not in ops.FORMATS:
+            raise ValueError(f"LPIPS: mode must be one of {tuple(ops.FORMATS)} (got {mode!r})")
+        self.mode, self.band_rows = mode, int(band_rows)
+        self.device = torch.device("cuda" if device is None else device)
+        if self.device.type != "cuda":
+            raise RuntimeError(f"LPIPS: needs a HIP device (got {self.device}); the kernels have no CPU fallback")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if [tuple(w.shape) for w in weights["conv"]] != [(c, 32 if l == 0 else 9 * LPIPS_WIDTHS[l - 1])
+                                                         for l, c in enumerate(LPIPS_WIDTHS)]:
+            raise ValueError("LPIPS: weights['conv'] must hold load_lpips_weights' 13 matrices")
+        with torch.cuda.device(self.device):
+            pk = ops.ImagePacker(mode)
+            self.images = []
+            for l, w in enumerate(weights["conv"]):
+                kpad = 64 if (l == 0 and mode == "bf16") else w.shape[1]
+                img = pk.image(ops.rup(w.shape[0], 128), kpad, self.device)
+                self.images.append(pk.put(img, w.to(self.device).contiguous()))
+            pk.run()
+        self.bias = [b.to(self.device).float().contiguous() for b in weights["bias"]]
+        self.lin = [v.to(self.device).float().contiguous() for v in weights["lin"]]
+        self._ws = {}
+
+    def _workspace(self, H, W):
+        ws = self._ws.get((H, W))
+        if ws is None:
+            need = int(_lib.load().cn_lpips_workspace_bytes(H, W, self.band_rows, ops.FORMATS[self.mode]))
+            if need == 0:
+                raise ValueError(f"LPIPS: images of {H} x {W} (each side at least 16): {_lib.load().cn_last_error().decode()}")
+            ws = self._ws[(H, W)] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return ws
+
+    def _terms(self, pred, gt):
+        a, b = _batched(pred, gt, "LPIPS")
+        for t in (a, b):
+            if not t.is_cuda or t.device != self.device or t.dtype != torch.float32 or t.shape[1] != 3:
+                raise RuntimeError(f"LPIPS: fp32 [3, H, W] or [N, 3, H, W] tensors on {self.device} expected (got "
+                                   f"{t.dtype} {tuple(t.shape)} on {t.device}); the kernels have no CPU fallback")
+        N, _, H, W = a.shape
+        ws = self._workspace(H, W)
+        out = torch.empty(N, 6, device=self.device, dtype=torch.float32)
+        d = _lib.LpipsDesc()
+        d.H, d.W, d.mfma_dtype, d.band_rows = H, W, ops.FORMATS[self.mode], self.band_rows
+        for l in range(_lib.LPIPS_CONVS):
+            d.weights[l], d.bias[l] = self.images[l].data_ptr(), self.bias[l].data_ptr()
+        for t in range(_lib.LPIPS_TAPS):
+            d.lin[t] = self.lin[t].data_ptr()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        for i in range(N):  # one pair per call: the pairs share the workspace, in the stream's order
+            d.pred, d.gt, d.out = a[i].data_ptr(), b[i].data_ptr(), out[i].data_ptr()
+            _lib.call("cn_lpips", ctypes.byref(d), ws.data_ptr(), ws.numel(), stream)
+        return out
+
+    def layers(self, pred, gt):
+        """The five per-block terms of every pair: [N, 5] on the device."""
+        return self._terms(pred, gt)[:, :5]
+
+    def __call__(self, pred, gt):
+        """[N] on the device: per pair the fp32 sum of the five terms in block order."""
+        return self._terms(pred, gt)[:, 5]
 
 
 # ---------------------------------------------------------------------------

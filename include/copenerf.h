@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CN_ABI_VERSION 19
+#define CN_ABI_VERSION 20
 
 typedef void* cn_stream_t; /* hipStream_t */
 
@@ -1032,6 +1032,83 @@ int cn_visual_images(int32_t H, int32_t W, const float* rgb, const float* depth,
                      const float* weighted_z, const float* normal, const float* flow, float* stats,
                      uint8_t* img, uint8_t* disparity, uint8_t* disparity_hw, uint8_t* normal_img,
                      uint8_t* flow_img, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
+ * LPIPS (VGG16, the v0.1 linear heads) from user-supplied weights (ABI v20): what
+ * co3d_metric.lpips(pred, gt, net_type="vgg") computes for eval.py:190-221
+ * (lpipsPyTorch/modules/{lpips,networks,utils}.py), for one pair of [3][H][W] images in
+ * [0, 1] (no 2x - 1 rescale), instead of 26 library convolutions and about sixty
+ * elementwise launches per pair:
+ *   1. z = (x - mean) / std per channel, mean (-.030, -.088, -.188), std (.458, .448, .450);
+ *   2. VGG16 features[0:30]: thirteen 3 x 3 convolutions (stride 1, zero padding 1, bias,
+ *      ReLU) of widths 64 64 | 128 128 | 256 256 256 | 512 512 512 | 512 512 512, a 2 x 2
+ *      stride-2 max-pool between the five blocks (floor: an odd last row / column is
+ *      dropped); the last activation of each block is tapped;
+ *   3. each tap unit-normalised over its channels: f^ = f / (sqrt(sum_c f^2) + 1e-10);
+ *   4. term_b = mean over the block's pixels of sum_c lin_b[c] (fx^ - fy^)^2.
+ * The library ships and fetches no weights: the caller passes them.
+ *
+ * cn_lpips_patches: the convolution's operand rows.  For output rows [y0, y0 + rows) of n
+ * maps, out [n rows Wo][kpad], row (i rows + r) Wo + x, column (dy 3 + dx) C + c = the
+ * source at (y0 + r + dy - 1, x + dx - 1, c) of map i, zero outside the map; columns
+ * [9 C, kpad) are zero.  mode 0: src is an NHWC map [n][Hs][Ws][C] (Ho = Hs, Wo = Ws);
+ * mode 1: the source is the 2 x 2 floor max-pool of that stored map, taken on read
+ * (Ho = Hs / 2, Wo = Ws / 2); mode 2 (C = 3, n <= 2): src and src1 are planar images
+ * [3][Hs][Ws], z-scored on read with a true fp32 division.  C a power of two in
+ * [4, 4096] (modes 0, 1), kpad a multiple of 4; loads along c and stores are 16 bytes
+ * (src, out 16-byte aligned); row offsets are 64-bit.
+ *
+ * cn_lpips_head: one block's term from its two NHWC taps fx, fy [P][C] (P pixels, C a
+ * power of two in [16, 512]) and lin [C]: out[0] = (sum_p sum_c lin[c] (fx^ - fy^)^2) / P.
+ * min(64, C / 4) lanes per pixel, one pass; one fp32 partial per workgroup of 64 pixels
+ * (lanes, then waves, in a fixed order); a second kernel sums the partials in a fixed
+ * order in double, divides by P and rounds once.  No atomics: bitwise reproducible;
+ * fx == fy gives exactly 0.  Workspace (256-byte aligned): ceil(P / 64) x 4 bytes,
+ * rounded up to 256.
+ *
+ * cn_lpips: the whole metric for one pair.  Each convolution is cn_lpips_patches into the
+ * workspace, then cn_linear (CN_EPI_RELU) on the caller's packed weights; both images are
+ * one batch of two, so a weight image is read once per band.
+ *   weights[l]: the image cn_pack_weights builds (format = mfma_dtype) from the layer's
+ *     [Cout][Kpad] matrix with columns (dy 3 + dx) Cin + c, padded with zero rows to a
+ *     multiple of 128 rows; Kpad = 9 Cin, and for the first layer 32 (CN_MFMA_BF16: 64);
+ *   bias[l] [Cout], lin[b] [C_b] fp32, 16-byte aligned;
+ *   mfma_dtype: CN_MFMA_F32_BF16X6 (the default of the Python side), CN_MFMA_BF16 or
+ *     CN_MFMA_F32;
+ *   band_rows: the patch matrix holds at most this many output rows of a layer at a time
+ *     (both images); 0 = the library's choice: per layer the most rows that keep the patch
+ *     matrix within 576 MiB (at least one row).  A layer's bands are of equal height up
+ *     to one row (540 x 960: conv1_2 in four bands of 135 rows, conv2_2 in two, every
+ *     other layer in one).  Only the
+ *     patch matrix is banded, the maps are whole, and a GEMM row depends on its own
+ *     operand row alone: out does not depend on band_rows, bit for bit;
+ *   out [6] (DEVICE): the five terms in block order, then their fp32 sum in that order.
+ * The terms are part of the contract (a test localises an error with them).
+ * Workspace (256-byte aligned): two maps of 2 H W 64 floats, the patch matrix, the heads'
+ * partials, each rounded up to 256 bytes.  Nothing is allocated, nothing synchronises.
+ * H or W < 16 (a block would be empty), H W > 2^26, band_rows < 0, a bad mfma_dtype, a
+ * NULL pointer anywhere in the descriptor, a workspace that is NULL or too small:
+ * CN_ERR_SHAPE (cn_lpips_workspace_bytes: 0 for the first four).
+ * ------------------------------------------------------------------------ */
+typedef struct cn_lpips_desc {
+    const float* pred;        /* [3][H][W] */
+    const float* gt;          /* [3][H][W] */
+    int32_t H, W;
+    const void* weights[13];
+    const float* bias[13];
+    const float* lin[5];
+    int32_t mfma_dtype;
+    int32_t band_rows;
+    float* out;               /* [6] */
+} cn_lpips_desc;
+
+int cn_lpips_patches(int32_t mode, int32_t n, int32_t Hs, int32_t Ws, int32_t C, const float* src,
+                     const float* src1, int32_t y0, int32_t rows, int32_t kpad, float* out, cn_stream_t stream);
+size_t cn_lpips_head_workspace_bytes(int64_t P);
+int cn_lpips_head(int32_t C, int64_t P, const float* fx, const float* fy, const float* lin, float* out,
+                  void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+size_t cn_lpips_workspace_bytes(int32_t H, int32_t W, int32_t band_rows, int32_t mfma_dtype);
+int cn_lpips(const cn_lpips_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
 
 #ifdef __cplusplus
 }

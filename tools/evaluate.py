@@ -3,6 +3,7 @@
     python tools/evaluate.py CHECKPOINT --images test.npy --K K.npy --world-mats w2c.npy --times t.npy --out OUT
         [--scale-mat S.npy] [--depths depths.npy] [--gt-poses gt.npy --pred-poses pred.npy]
         [--depth-range 0.01 5.0] [--chunk 65536] [--mode fp32|bf16x6|bf16]
+        [--lpips-vgg vgg16.pth --lpips-lin vgg.pth]
 
   CHECKPOINT    one train.py wrote through CheckpointIO (see tools/extract_mesh.py)
   --images      .npy (or .npz with `imgs`): float [N, 3, H, W], the test frames (planar, as the reference's)
@@ -12,9 +13,11 @@
   --depths      .npy (or .npz with `depths`) [N, h, w]: ground-truth depth, any resolution; without it no depth
                 metrics (the reference's `-1`)
   --gt-poses, --pred-poses   .npy / .pt [M, 4, 4] camera-to-world trajectories for the pose metrics
+  --lpips-vgg, --lpips-lin   the two LPIPS weight files (both or neither): torchvision's VGG16 state dict and
+                LPIPS v0.1's vgg.pth (copenerf.metrics.load_lpips_weights).  Nothing is ever downloaded.
 
-Writes OUT/results.txt in eval.py:268-270's format: PSNR, SSIM, then rpe_trans, rpe_rot, ate, then the seven
-depth errors.  LPIPS is not computed: its network weights are not part of this build."""
+Writes OUT/results.txt in eval.py:268-270's format: PSNR, SSIM, LPIPS (only with the two weight files), then
+rpe_trans, rpe_rot, ate, then the seven depth errors."""
 import argparse
 import os
 import sys
@@ -50,7 +53,11 @@ def main(argv=None):
     ap.add_argument("--depth-range", type=float, nargs=2, default=[0.01, 5.0])
     ap.add_argument("--chunk", type=int, default=65536)
     ap.add_argument("--mode", choices=["fp32", "bf16x6", "bf16"], default="bf16x6", help="the MLP GEMMs' MFMA mode")
+    ap.add_argument("--lpips-vgg", default=None, help="torchvision VGG16 state dict (features.N.weight / bias)")
+    ap.add_argument("--lpips-lin", default=None, help="LPIPS v0.1 vgg.pth (linN.model.1.weight)")
     a = ap.parse_args(argv)
+    if (a.lpips_vgg is None) != (a.lpips_lin is None):
+        raise SystemExit("--lpips-vgg and --lpips-lin go together")
     if not torch.cuda.is_available():
         raise SystemExit("evaluate: needs a HIP device (the kernels have no CPU fallback)")
     from copenerf import metrics
@@ -77,9 +84,12 @@ def main(argv=None):
         raise SystemExit("--gt-poses and --pred-poses go together")
     gt_poses = None if a.gt_poses is None else _load(a.gt_poses, "poses")
     pred_poses = None if a.pred_poses is None else _load(a.pred_poses, "poses")
+    lpips_fn = None
+    if a.lpips_vgg is not None:
+        lpips_fn = metrics.LPIPS(metrics.load_lpips_weights(a.lpips_vgg, a.lpips_lin), device=dev)
     r = build_renderer(a.checkpoint).to(dev).set_mfma_dtype(a.mode)
     res = metrics.evaluate(r, views, depth_range=tuple(a.depth_range), gt_poses=gt_poses, pred_poses=pred_poses,
-                           gt_depths=depths, chunk=a.chunk)
+                           gt_depths=depths, lpips_fn=lpips_fn, chunk=a.chunk)
     os.makedirs(a.out, exist_ok=True)
     path = os.path.join(a.out, "results.txt")
     metrics.write_results(path, res)
