@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libcopenerf.so"
 LIB_PATH = os.environ.get("COPENERF_LIB", os.path.join(_HERE, LIB_NAME))
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 c_f32p = ctypes.c_void_p  # device pointers are passed as integers
 c_i32 = ctypes.c_int32
@@ -279,6 +279,11 @@ SIGNATURES = {
     "cn_lpips_head": (c_i32, [c_i32, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
     "cn_lpips_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32, c_i32]),
     "cn_lpips": (c_i32, [ctypes.POINTER(LpipsDesc), c_ptr, c_i64, c_ptr]),
+    "cn_flow_rgb_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32]),
+    "cn_flow_rgb_fwd": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
+    "cn_flow_rgb_bwd": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
 }
 
 _lock = threading.Lock()

@@ -5,6 +5,7 @@
   scene_flow_loss                 train.py:467-477 (sdf_loss)
   project_flow / warp_pixel       train.py:478-496, 235-244 (flow-RGB warp)
   stage1_terms_fused              train.py:467-504 per-sample work in one HIP pass each way
+  flow_rgb_fused                  train.py:479-517 flow projection + flow-RGB loss in one HIP pass each way
   sdf_consistency_points          train.py:497-505
 
 The motion network maps a time step to an angular and a linear velocity.  It is
@@ -468,6 +469,76 @@ def flow_rgb_loss(flow_fw, sampled_pixel, ref_img, rgb_gt, group=None):
     den = _allreduce_sum(torch.sum(valid, dim=(1, 2)).float(), group)
     out = _world(group) * num / (den + 1e-10)
     return out[0] if single else out
+
+
+class _FlowRgbTerms(torch.autograd.Function):
+    """cn_flow_rgb_fwd / cn_flow_rgb_bwd: project_flow_sums and the sums of flow_rgb_loss for T
+    reference frames read in place from the image stack, one HIP pass each way.  Outputs
+    (num [T], count [T]): the masked L1 sums and the numbers of valid rays (no gradient).
+    Gradients reach ray_acc and w2c only, as in the composition (the mask is detached; the
+    cameras, pixels, targets and images are data).  The backward recomputes the forward."""
+
+    @staticmethod
+    def forward(ctx, ray_acc, w2c, KS, pixn, pix, rgb_gt, images, frame, frame_valid):
+        from . import ops
+        args = (ray_acc.contiguous(), w2c.contiguous(), KS.contiguous(), pixn.contiguous(), pix.contiguous(),
+                rgb_gt.contiguous(), images, frame, frame_valid)
+        sums = ops.flow_rgb_fwd(*args)
+        ctx.save_for_backward(*args[:8])
+        ctx.frame_valid = frame_valid  # (None, or a mask: not a tensor autograd tracks)
+        num, count = sums[:, 0], sums[:, 1]
+        ctx.mark_non_differentiable(count)
+        return num, count
+
+    @staticmethod
+    def backward(ctx, g_num, _g_count):
+        from . import ops
+        saved = ctx.saved_tensors
+        w2c = saved[1]
+        T = w2c.shape[0]
+        g_num = torch.zeros(T, device=w2c.device) if g_num is None else g_num.float().contiguous()
+        d_ray, d_w2c = ops.flow_rgb_bwd(*saved, ctx.frame_valid, g_num)
+        d_w2c = torch.cat([d_w2c, d_w2c.new_zeros(T, 1, 4)], 1) if ctx.needs_input_grad[1] else None
+        return (d_ray if ctx.needs_input_grad[0] else None, d_w2c) + (None,) * 7
+
+
+def _ray_acc_of(pbar, wbar):
+    """[R, 4] = (pbar, wbar): the buffer itself when the two are the column slices of one
+    (stage1_terms_fused returns ray_acc[:, :3], ray_acc[:, 3:]), else their concatenation."""
+    base = pbar._base
+    R = pbar.shape[0]
+    if (base is not None and base is wbar._base and tuple(base.shape) == (R, 4) and base.is_contiguous() and
+            tuple(pbar.shape) == (R, 3) and tuple(wbar.shape) == (R, 1) and
+            pbar.stride() == (4, 1) and wbar.stride(0) == 4 and
+            pbar.storage_offset() == base.storage_offset() and wbar.storage_offset() == base.storage_offset() + 3):
+        return base
+    return torch.cat([pbar.reshape(R, 3), wbar.reshape(R, 1)], 1)
+
+
+def flow_rgb_fused(pbar, wbar, w2c, ref_camera_mat, scale_mat, normalized_pixels, sampled_pixel, images, frame_idx,
+                   rgb_gt, frame_valid=None, group=None):
+    """flow_rgb_loss(project_flow_sums(pbar, wbar, w2c, ref_camera_mat, scale_mat, normalized_pixels,
+    (H, W)), sampled_pixel, images[frame_idx], rgb_gt) in one HIP pass each way (cn_flow_rgb_fwd /
+    cn_flow_rgb_bwd): per-frame losses [T] for w2c [T, 4, 4], ref_camera_mat [T, 4, 4], the resident
+    stack images [N, 3, H, W] (fp32, contiguous) and frame_idx [T] device indices into it, read by the
+    kernel (no frame is copied, and a captured launch follows the indices).  A frame with
+    frame_valid[t] false, or an index outside the stack, is not read and gives an exact zero.  A ray
+    whose correspondence is not finite counts as outside the image (torch would carry the NaN).
+    Σvalid is all-reduced with a process group, as in flow_rgb_loss."""
+    if w2c.dim() != 3:
+        raise ValueError("flow_rgb_fused: w2c must be [T, 4, 4] (stack a single frame as [1, 4, 4])")
+    T = w2c.shape[0]
+    KS = scale_mat.reshape(-1, 4, 4)[0, :3, :3] @ ref_camera_mat.reshape(-1, 4, 4)[:, :3, :3]  # [T, 3, 3]
+    if KS.shape[0] != T:
+        KS = KS.expand(T, 3, 3)
+    frame = frame_idx.reshape(T).to(torch.int64).contiguous()
+    if frame_valid is not None:
+        fv = frame_valid.reshape(T)
+        frame_valid = (fv if fv.dtype == torch.bool else fv != 0).contiguous().view(torch.uint8)
+    num, count = _FlowRgbTerms.apply(_ray_acc_of(pbar, wbar), w2c, KS.detach(), normalized_pixels.detach(),
+                                     sampled_pixel.detach(), rgb_gt.detach(), images.detach(), frame, frame_valid)
+    den = _allreduce_sum(count, group)
+    return _world(group) * num / (den + 1e-10)
 
 
 def world_points(pts, cw2):

@@ -1185,6 +1185,69 @@ def refine_warp(images, depth, tgt, src, pose, K, Kinv, want_warped=False):
 
 
 # ---------------------------------------------------------------------------
+# The flow-RGB term of stage 1 (ABI v21)
+def _flow_rgb_args(fn, ray_acc, w2c, KS, pixn, pix, rgb_gt, images, frame, frame_valid):
+    """Check the common inputs of cn_flow_rgb_fwd / _bwd; returns (R, T, N, H, W, the pointer arguments)."""
+    for t, name in ((ray_acc, "ray_acc"), (w2c, "w2c"), (KS, "KS"), (pixn, "pixn"), (pix, "pix"), (rgb_gt, "rgb_gt"),
+                    (images, "images")):
+        _need(t, name, ndim=0)
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != images.device:
+            raise RuntimeError(f"{fn}: {name} must be a contiguous fp32 tensor on the images' device")
+    if images.dim() != 4 or images.shape[1] != 3:
+        raise RuntimeError(f"{fn}: images must be [N, 3, H, W] (got {tuple(images.shape)})")
+    N, _, H, W = images.shape
+    R, T = ray_acc.shape[0], w2c.shape[0]
+    for t, name, shape in ((ray_acc, "ray_acc", (R, 4)), (w2c, "w2c", (T, 4, 4)), (KS, "KS", (T, 3, 3)),
+                           (pixn, "pixn", (R, 2)), (pix, "pix", (R, 2)), (rgb_gt, "rgb_gt", (R, 3))):
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f"{fn}: {name} must be {list(shape)} (got {list(t.shape)})")
+    if (frame.dtype != torch.int64 or tuple(frame.shape) != (T,) or not frame.is_contiguous() or
+            frame.device != images.device):
+        raise RuntimeError(f"{fn}: frame must be a contiguous int64 [{T}] tensor on the images' device")
+    if frame_valid is not None and (frame_valid.dtype != torch.uint8 or tuple(frame_valid.shape) != (T,) or
+                                    not frame_valid.is_contiguous() or frame_valid.device != images.device):
+        raise RuntimeError(f"{fn}: frame_valid must be a contiguous uint8 [{T}] tensor on the images' device")
+    return R, T, N, H, W, (_ptr(ray_acc), _ptr(w2c), _ptr(KS), _ptr(pixn), _ptr(pix), _ptr(rgb_gt), _ptr(images),
+                           _ptr(frame), _ptr(frame_valid))
+
+
+def _flow_rgb_workspace(fn, R, T, dev):
+    need = int(_lib.load().cn_flow_rgb_workspace_bytes(R, T))
+    if need == 0:  # a shape the library refuses: let it say why
+        _lib.check(_lib.load().cn_flow_rgb_fwd(R, T, 1, 1, 1, *([None] * 11), 0, None), fn)
+    return torch.empty(need, dtype=torch.uint8, device=dev), need
+
+
+def flow_rgb_fwd(ray_acc, w2c, KS, pixn, pix, rgb_gt, images, frame, frame_valid=None):
+    """cn_flow_rgb_fwd: ray_acc [R, 4], w2c [T, 4, 4], KS [T, 3, 3], pixn / pix [R, 2], rgb_gt [R, 3], images
+    [N, 3, H, W] (fp32, contiguous, one device), frame int64 [T], frame_valid uint8 [T] or None.  Returns sums
+    fp32 [T, 2]: the masked L1 sum and the number of valid rays of each reference frame."""
+    R, T, N, H, W, ptrs = _flow_rgb_args("flow_rgb_fwd", ray_acc, w2c, KS, pixn, pix, rgb_gt, images, frame, frame_valid)
+    dev = images.device
+    ws, need = _flow_rgb_workspace("cn_flow_rgb_fwd", R, T, dev)
+    sums = torch.empty(T, 2, device=dev, dtype=torch.float32)
+    _lib.call("cn_flow_rgb_fwd", R, T, N, H, W, *ptrs, _ptr(sums), _ptr(ws), need,
+              torch.cuda.current_stream(dev).cuda_stream)
+    return sums
+
+
+def flow_rgb_bwd(ray_acc, w2c, KS, pixn, pix, rgb_gt, images, frame, frame_valid, g_num):
+    """cn_flow_rgb_bwd: the inputs of flow_rgb_fwd and g_num fp32 [T] = d loss / d sums[:, 0].  Returns
+    (d_ray_acc [R, 4], d_w2c [T, 3, 4])."""
+    R, T, N, H, W, ptrs = _flow_rgb_args("flow_rgb_bwd", ray_acc, w2c, KS, pixn, pix, rgb_gt, images, frame, frame_valid)
+    dev = images.device
+    if (g_num.dtype != torch.float32 or tuple(g_num.shape) != (T,) or not g_num.is_contiguous() or
+            g_num.device != dev):
+        raise RuntimeError(f"flow_rgb_bwd: g_num must be a contiguous fp32 [{T}] tensor on the images' device")
+    ws, need = _flow_rgb_workspace("cn_flow_rgb_bwd", R, T, dev)
+    d_ray = torch.empty(R, 4, device=dev, dtype=torch.float32)
+    d_w2c = torch.empty(T, 3, 4, device=dev, dtype=torch.float32)
+    _lib.call("cn_flow_rgb_bwd", R, T, N, H, W, *ptrs, _ptr(g_num), _ptr(d_ray), _ptr(d_w2c), _ptr(ws), need,
+              torch.cuda.current_stream(dev).cuda_stream)
+    return d_ray, d_w2c
+
+
+# ---------------------------------------------------------------------------
 # Evaluation metrics (ABI v18)
 def ssim_taps():
     """The 11 window weights by the reference's own expression (co3d_metric.py:49-51): exp in Python

@@ -42,8 +42,8 @@ import torch.distributed as dist
 
 from .fields import RenderingNetwork, SDFNetwork, SingleVarianceNetwork
 from .losses import EdgePreservingSmoothnessLoss, SmoothnessLoss, eikonal_loss, rgb_l1, train_losses
-from .motion import (MotionNetwork, affine_points, flow_rgb_loss, masked_chain, mat4_chain, project_flow,
-                     project_flow_sums,
+from .motion import (MotionNetwork, affine_points, flow_rgb_fused, flow_rgb_loss, masked_chain, mat4_chain,
+                     project_flow, project_flow_sums,
                      scene_flow_loss, stage1_terms_fused)
 from .rays import PoseRetriever, get_patch_indices, intrinsics_ndc, inv4x4, pixels_from_indices, world_rays
 from .renderer import NeuSRenderer
@@ -64,6 +64,7 @@ TRAIN_CFG = dict(learning_rate=1e-3, pose_learning_rate=5e-4, rgb_weight=1.0, ei
                  end_consistency_weight_increase_iteration=100000, patch_size=4, world_idx="mid",
                  random_ref_interval=(1, 2, 3), neus_anneal_end=50000, s=1,
                  sdf_consistency_enable_pose_grad=False)
+FLOW_RGB_MODES = ("torch", "fused")  # SyntheticTrainer(flow_rgb=...)
 PAIR_WEIGHTS = ("sdf_weight", "flow_rgb_weight", "sdf_consistency_weight", "edge_aware_smoothness_weight",
                 "smoothness_weight")
 
@@ -198,9 +199,16 @@ class SyntheticTrainer:
     def __init__(self, device, rays=4096, H=540, W=960, patch=4, seed=678, depth_range=(0.01, 5.0),
                  cos_anneal_ratio=0.5, schedule="fixed", start_it=0, distributed=False, group=None,
                  sdf_cfg=None, col_cfg=None, ren_cfg=None, joint_pose=False, stage1=False, n_images=10,
-                 capturable=False, mfma_dtype="fp32", train_cfg=None, stage1_fused=True, small_gemm_blas=True):
+                 capturable=False, mfma_dtype="fp32", train_cfg=None, stage1_fused=True, small_gemm_blas=True,
+                 flow_rgb="torch"):
         if schedule not in ("fixed", "reference"):
             raise ValueError(f"schedule must be 'fixed' or 'reference' (got {schedule!r})")
+        if flow_rgb not in FLOW_RGB_MODES:
+            raise ValueError(f"flow_rgb must be one of {FLOW_RGB_MODES} (got {flow_rgb!r})")
+        # the flow projection + flow-RGB loss of stage 1: "torch" (the op chain of motion.project_flow_sums /
+        # flow_rgb_loss over a copy of the reference frames) or "fused" (motion.flow_rgb_fused: one HIP pass
+        # each way over the resident stack); may be changed between steps
+        self.flow_rgb = flow_rgb
         self.small_gemm_blas = small_gemm_blas  # rocBLAS for torch's small GEMMs inside the steps only
         self.device = torch.device(device)
         self.R, self.H, self.W, self.patch = rays, H, W, patch
@@ -371,21 +379,34 @@ class SyntheticTrainer:
             c2c = masked_chain(P, lo, hi)
             cw2 = torch.where(img.view(1, 1) >= w, inv4x4(c2c), c2c)
         pts = out["sampled_points"]
+        if self.flow_rgb not in FLOW_RGB_MODES:
+            raise ValueError(f"flow_rgb must be one of {FLOW_RGB_MODES} (got {self.flow_rgb!r})")
+        fused_flow = self.flow_rgb == "fused"
+        cams = self.camera_mats.index_select(0, refc)
         if self.stage1_fused:
             # one HIP pass each way over the samples (cn_stage1_fwd / cn_stage1_bwd)
             sdf_loss, pbar, wbar, x = stage1_terms_fused(pts, out["normals"], out["sdf_flows"], out["weights"], omega,
                                                          vel, cw2, self.world_time_step, pose_grad, group=grp)
-            flows = project_flow_sums(pbar, wbar, w2c, self.camera_mats.index_select(0, refc), self.I, batch["pixn"],
-                                      (self.H, self.W))
+            if not fused_flow:
+                flows = project_flow_sums(pbar, wbar, w2c, cams, self.I, batch["pixn"], (self.H, self.W))
         else:  # the same terms as torch expressions (the parity test's reference: stage1_fused=False)
             sdf_loss = scene_flow_loss(pts, out["normals"], out["sdf_flows"], out["weights"], omega, vel, group=grp)
-            flows = project_flow(pts, out["weights"], w2c, self.camera_mats.index_select(0, refc), self.I,
-                                 batch["pixn"], (self.H, self.W))
+            if fused_flow:  # the per-ray sums of project_flow
+                wr = out["weights"].reshape(R, -1, 1)
+                pbar, wbar = torch.sum(wr * pts.reshape(R, -1, 3), dim=1), torch.sum(wr, dim=1)
+            else:
+                flows = project_flow(pts, out["weights"], w2c, cams, self.I, batch["pixn"], (self.H, self.W))
             with torch.set_grad_enabled(pose_grad):
                 pw = affine_points(pts.reshape(-1, 3), cw2)
                 x = torch.cat([pw, torch.full_like(pw[:, :1], self.world_time_step)], 1)
-        per = flow_rgb_loss(flows, batch["pix"], self.images.index_select(0, refc), batch["rgb_gt"], group=grp)
-        flow_rgb = torch.where(valid, per, torch.zeros_like(per)).sum() / 3.0
+        if fused_flow:
+            # cn_flow_rgb_fwd / _bwd: the frames are read in place, a masked frame is an exact zero
+            per = flow_rgb_fused(pbar, wbar, w2c, cams, self.I, batch["pixn"], batch["pix"], self.images, refc,
+                                 batch["rgb_gt"], frame_valid=valid, group=grp)
+            flow_rgb = per.sum() / 3.0
+        else:
+            per = flow_rgb_loss(flows, batch["pix"], self.images.index_select(0, refc), batch["rgb_gt"], group=grp)
+            flow_rgb = torch.where(valid, per, torch.zeros_like(per)).sum() / 3.0
         # SDFNetwork.sdf (train.py:504) on the weights the renderer packed for this step
         pack, self.renderer.last_sdf_pack = self.renderer.last_sdf_pack, None
         sdf_w = self.sdf.field(x, want_feat=False, want_grad=False, packed=pack)[0]

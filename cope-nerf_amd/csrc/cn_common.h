@@ -71,6 +71,22 @@ __device__ __forceinline__ float softplus_grad_ref(float x, float beta, float th
 
 __host__ __device__ __forceinline__ int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// grid_sample's border clip of an unnormalised coordinate (GridSampler.h clip_coordinates_set_grad):
+// the clamped coordinate, *mult = 0 where it was clamped (the borders count as clamped).  Shared by the
+// two bilinear warps (cn_refine.hip, cn_flow_rgb.hip).
+__device__ __forceinline__ float clip_border(float x, float maxv, float* mult) {
+    if (!(x > 0.0f)) {  // (a NaN coordinate samples texel 0, as fmax(x, 0))
+        *mult = 0.0f;
+        return 0.0f;
+    }
+    if (x >= maxv) {
+        *mult = 0.0f;
+        return maxv;
+    }
+    *mult = 1.0f;
+    return x;
+}
+
 }  // namespace cn
 
 #define CN_REQUIRE(cond, code, ...)           \

@@ -42,21 +42,6 @@ struct RefineArgs {
     int tiles_x;
 };
 
-// grid_sample's border clip of an unnormalised coordinate (GridSampler.h clip_coordinates_set_grad):
-// the clamped coordinate, *mult = 0 where it was clamped (the borders count as clamped)
-__device__ __forceinline__ float clip_border(float x, float maxv, float* mult) {
-    if (!(x > 0.0f)) {  // (a NaN coordinate samples texel 0, as fmax(x, 0))
-        *mult = 0.0f;
-        return 0.0f;
-    }
-    if (x >= maxv) {
-        *mult = 0.0f;
-        return maxv;
-    }
-    *mult = 1.0f;
-    return x;
-}
-
 __global__ void __launch_bounds__(256) refine_warp_kernel(RefineArgs a) {
     __shared__ float smem[4 * 14];
     const int j = blockIdx.y;

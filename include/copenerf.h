@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CN_ABI_VERSION 20
+#define CN_ABI_VERSION 21
 
 typedef void* cn_stream_t; /* hipStream_t */
 
@@ -1109,6 +1109,57 @@ int cn_lpips_head(int32_t C, int64_t P, const float* fx, const float* fy, const 
                   void* workspace, int64_t workspace_bytes, cn_stream_t stream);
 size_t cn_lpips_workspace_bytes(int32_t H, int32_t W, int32_t band_rows, int32_t mfma_dtype);
 int cn_lpips(const cn_lpips_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
+ * The flow-RGB term of stage 1 (ABI v21): the flow projection of train.py:484-495 from
+ * the per-ray sums of cn_stage1_fwd, warp_pixel (train.py:235-244) and the masked L1 of
+ * train.py:506-515 for T reference frames, one launch and one fixed-order reduction each
+ * way instead of a chain of torch ops and a copy of T frames out of the image stack.
+ *   ray_acc [R][4]    (sum_s w p, sum_s w) per ray (cn_stage1_fwd's), 16-byte aligned;
+ *   w2c [T][4][4]     the relative poses (row 3 is not read);
+ *   KS [T][3][3]      scale_mat[:3,:3] ref_camera_mat[t][:3,:3];
+ *   pixn, pix [R][2]  the rays' normalised and pixel coordinates (x, y); rgb_gt [R][3];
+ *   images [N][3][H][W] planar; frame [T]: int64 indices into the stack, read on the
+ *     device (a captured launch follows their current values);
+ *   frame_valid [T]: NULL, or one byte per frame (0: masked).
+ * Per frame t and ray r, all fp32 without contraction:
+ *   wp = w2c[t][:3,:3] pbar + wbar w2c[t][:3,3],  q = KS[t] wp,  n = (q0, q1) / q2
+ *   corr  = pix + (n - pixn) * (W/2, H/2)
+ *   valid = 0 <= corr.x < W and 0 <= corr.y < H
+ *   warp  = the bilinear sample of images[frame[t]] at corr, border padding,
+ *           align_corners=True (sampled at corr itself: the reference normalises to
+ *           [-1, 1] and grid_sample un-normalises, which differs by rounding)
+ *   sums [T][2] = (sum over valid rays and the 3 channels of |warp - rgb_gt|, the number
+ *                  of valid rays)
+ * A frame with frame_valid[t] = 0 or an index outside [0, N) is never read and gives
+ * exact zeros (sums, d_w2c[t], its share of d_ray_acc).  A ray whose correspondence is
+ * not finite (q2 = 0, a NaN input) fails every comparison of the mask and counts as
+ * invalid; torch's composition would carry the NaN into the sum instead.
+ * cn_flow_rgb_bwd: g_num [T] (device) = d loss / d sums[t][0];
+ *   d_ray_acc [R][4] (16-byte aligned) = sum over t = 0 .. T-1, in that order, of the
+ *     ray's gradient; d_w2c [T][12] = row-major d / d w2c[t][:3,:].
+ *   sign(warp - gt) with sign(0) = 0, the bilinear derivative zero where the coordinate
+ *   was clamped (torch's border rule), the quotient rule, KS^T, then w2c^T / the outer
+ *   product with (pbar, wbar).  No gradient through the mask, KS, pix, pixn, rgb_gt or
+ *   the images.  The backward recomputes the projection and re-reads the taps.
+ * Reduction: one partial per 64 rays and frame, summed in a fixed order; no atomics.
+ * Bitwise reproducible; a frame's sums and d_w2c do not depend on the other frames.
+ * The valid counts are exact.  Frame base offsets are 64-bit.
+ * T outside 1 .. 8, R < 0, N < 1, H or W < 1, 3 H W >= 2^31, a workspace that is NULL or
+ * too small: CN_ERR_SHAPE (cn_flow_rgb_workspace_bytes: 0 for the first two).  Workspace
+ * (256-byte aligned): ceil(max(R, 1) / 64) T x 48 bytes, rounded up to 256, for either
+ * call.  R = 0: the ray arrays may be NULL, nothing reads them, the sums / d_w2c are
+ * written as zeros.
+ * ------------------------------------------------------------------------ */
+size_t cn_flow_rgb_workspace_bytes(int32_t R, int32_t T);
+int cn_flow_rgb_fwd(int32_t R, int32_t T, int32_t N, int32_t H, int32_t W, const float* ray_acc, const float* w2c,
+                    const float* KS, const float* pixn, const float* pix, const float* rgb_gt, const float* images,
+                    const int64_t* frame, const uint8_t* frame_valid, float* sums, void* workspace,
+                    int64_t workspace_bytes, cn_stream_t stream);
+int cn_flow_rgb_bwd(int32_t R, int32_t T, int32_t N, int32_t H, int32_t W, const float* ray_acc, const float* w2c,
+                    const float* KS, const float* pixn, const float* pix, const float* rgb_gt, const float* images,
+                    const int64_t* frame, const uint8_t* frame_valid, const float* g_num, float* d_ray_acc,
+                    float* d_w2c, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
 
 #ifdef __cplusplus
 }
