@@ -196,6 +196,7 @@ class ImagePacker:
 # launch-class tags of the kernel timer: linear_kernel<WM, WN, TM, TN, BK, OCC, DEPTH, ...> arguments
 # (named by the library itself, cn_linear_kernel_name) -> a short tile name
 _TILE_TAGS = {"4, 2, 2, 4, 16, 1, 2": "sq", "4, 2, 1, 4, 32, 1, 2": "tall", "4, 2, 2, 2, 32, 1, 2": "wide",
+              "2, 2, 2, 4, 16, 2, 2": "tall2",
               "2, 2, 2, 2, 16, 2, 2": "t128", "4, 1, 1, 2, 16, 2, 2": "t1", "4, 2, 2, 4, 32, 1, 2": "sq",
               "2, 2, 2, 2, 64, 2, 1": "t128", "4, 1, 1, 2, 64, 2, 1": "t1"}
 
@@ -230,7 +231,8 @@ def linear(A, B, N, K, out0, epilogue, *, bias=None, A2=None, K1=None, rowv=None
     EPI_SOFTPLUS_HEAD (the last SDF hidden layer): out0 = softplus activation (or
     None: not stored), out1 = colv * softplus' (or None), head_out[head_idx[m] or m]
     = out0[m] · head_w + head_b.
-    tile: None (the library's choice), 1 (128x64), 2 (128x128 only: tests compare the tiles).
+    tile: None (the library's choice), 1 (128x64), 2 (128x128 only: tests compare the tiles); bf16x6 only:
+    3 (the two-per-CU 128x256 tile), 4 (the 256x256 tile), both for 128 < N <= 256 without rowv.
     bf16 operand images (bf16 MFMA mode only, ABI v10): A (with A2) may be bfloat16 -- the rounded
     operand itself, read instead of rounded on load; aux0 may be bfloat16 for BWD_RELU (its sign) and
     for MUL / TANGENT / BWD_SOFTPLUS (the activation σ is recovered from), BWD_SOFTPLUS's aux1 / aux2

@@ -83,6 +83,9 @@ struct LinearArgs {
 //         and aux2 are bf16 images.
 constexpr int kTblCols = 512;  // widest N with a bias / colv (the LDS column table)
 
+#ifndef CN_AB_TALL2_OFFSET
+#define CN_AB_TALL2_OFFSET 0  // (measurement) start delay of each CU's second 128x256 workgroup
+#endif
 #ifndef CN_DMA_A_NT
 #define CN_DMA_A_NT 0  // 1: the LDS-DMA ring's A chunks loaded non-temporally (measured slower: a 32-deep chunk is half a 128-byte line; profiles/r6_ab.txt r6x)
 #endif
@@ -112,7 +115,25 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
     constexpr int NPL = MODE == 2 ? 3 : 1;       // bf16 planes per operand
     // padded LDS row in dwords: 36 in every mode (BK = 32 f32 / 64 bf16 / 16 split: 3 x 8 + 12 pad)
     // (BK = 32 split: 3 x 16 + 4 pad = 52, conflict-free like wgrad_x6_kernel's rows)
-    constexpr int LS = (BF ? NPL * BK / 2 : BK) + (MODE == 2 && BK == 16 ? 12 : 4);
+    // The two-per-CU 128x256 bf16x6 tile (kRot) has unpadded rows of 24 dwords (96 bytes: terms 0, 1, 2 x 16
+    // bf16; 2 x (128 + 256) x 96 B = 72 KB, resident twice).  Rows r and r + 8 of such an image start on the
+    // same bank quad (8 x 24 = 192 = 3 x 64 dwords), so a row with (r >> 3) odd is stored with the two 16-byte
+    // k halves of every term exchanged: logical piece c (= 2 term + k half) of row r is physical piece
+    // c ^ (r >> 3 & 1).  (cn_sampler.hip's rows rotate their six pieces by one place instead, DESIGN.md §3.10:
+    // the same bank argument, but the rotation wraps, so the three terms' offsets are no longer 32 bytes apart
+    // and every read and write address takes three registers instead of one, 6 more in a kernel that sits at
+    // the 256 registers of two waves per SIMD.)
+    // A fragment read (ds_read_b128, bank = dword % 64, i.e. 16 quads of 4 banks) has every lane of a group on
+    // the same logical piece c and row l & 31 of a 32-row block (a block is 768 = 12 x 64 dwords: no shift).
+    // Quad of row r with exchange bit t: (6 r + (c ^ t)) % 16.  Lane group {0-3, 12-15, 20-27}: rows 0-3 give
+    // 6 r = {0, 6, 12, 2}, rows 20-23 {8, 14, 4, 10} (t = 0); rows 12-15 {8, 14, 4, 10}, rows 24-27 {0, 6, 12, 2}
+    // (t = 1).  So the t = 0 rows hold the quads c + {0, 2, 4, ..., 14} and the t = 1 rows (c ^ 1) + {0, 2, ...,
+    // 14}: c and c ^ 1 differ by 1, so the 16 quads are distinct.  Group {4-11, 16-19, 28-31}: rows 4-7
+    // {8, 14, 4, 10}, 16-19 {0, 6, 12, 2} (t = 0), rows 8-11 {0, 6, 12, 2}, 28-31 {8, 14, 4, 10} (t = 1): the same
+    // two sets.  Lanes 32-63 read the other k half (c ^ 1) of the same rows: the same argument.  Conflict-free
+    // for every c, on the A and the B fragments alike.
+    constexpr bool kRot = MODE == 2 && BK == 16 && OCC == 2 && TM * TN >= 8 && (MODE_ & 16) == 0;
+    constexpr int LS = kRot ? 24 : (BF ? NPL * BK / 2 : BK) + (MODE == 2 && BK == 16 ? 12 : 4);
     constexpr int EPA = ABF ? 8 : 4;             // A elements per 16-byte staging piece
     constexpr int ESA = ABF ? 2 : 4;             // bytes per A element
     constexpr int KC4 = BK / EPA;                // A: 16-byte pieces per staged row
@@ -154,6 +175,7 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
     constexpr bool kDma = ABF && MODE == 1 && TM * TN >= 8 && BK == 32 && OCC == 1 && BM == 256 && BN == 256;
     constexpr int DNS = 4, DROWB = BK * 2, DSIDEA = BM * DROWB, DSTAGE = (BM + BN) * DROWB;
     constexpr int LDS_MAIN = kDma ? DNS * DSTAGE / 4 + 2 * BM : LDS_FLOATS;
+    static_assert(!kRot || (LDS_MAIN + TBL) * 4 <= 80 * 1024, "two workgroups per CU: at most 80 KB each");
     __shared__ __attribute__((aligned(16))) float smem[LDS_MAIN + TBL];
     float* sA = smem;
     float* sB = smem + 2 * BM * LS;
@@ -199,6 +221,15 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
             const int h = idx / (BN * 6), w = idx % (BN * 6);
             voB[q] = idx < BN * KCB ? h * p.ldb * 96 + w * 16 : 0;
             ldsB[q] = (w / 6) * LS + ((w % 6) >> 1) * (BK / 2) + 8 * h + 4 * (w & 1);
+            if constexpr (kRot) {
+                // physical piece idx of the (unpadded) image is written as it is; the exchange is in the
+                // source offset: it holds logical piece (idx % 6) ^ (row >> 3 & 1) of row idx / 6
+                static_assert(!kRot || BN * KCB % NT == 0, "whole pieces per thread");
+                // (pieces idx and idx + 768 are 128 rows apart: same piece, same exchange -- said so, for the
+                // compiler keeps one register per distinct offset)
+                voB[q] = q >= 3 && 3 * NT == 768 ? voB[q - 3] + 128 * 96 : (w / 6) * 96 + ((w % 6) ^ ((w / 6) >> 3 & 1)) * 16;
+                ldsB[q] = idx * 4;
+            }
         } else {
             voB[q] = (srowb + q * RSTEPB) * p.ldb * ESZB + scb * 16;
         }
@@ -206,14 +237,23 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
     // LDS write offsets in dwords: A as fp32 float4 (4 dwords), bf16x4 (2 dwords) or a bf16x8 piece
     // (4 dwords); B 16-byte pieces
     const int lds_a = srow * LS + sc4 * (ABF || !BF ? 4 : 2);
+    // (kRot) the thread's 4 k (k quarter sc4: logical piece 2 t + sc4 / 2 of term t, its half sc4 % 2) within
+    // the row; RSTEP is a multiple of 16, so every row of the thread has the exchange bit of srow
+    static_assert(!kRot || RSTEP % 16 == 0, "one exchange bit per thread");
+    const int rotA = ((sc4 >> 1) ^ (srow >> 3 & 1)) * 4 + 2 * (sc4 & 1);
     const int lds_b = srowb * LS + scb * 4;
 
-    floatx4 ra[DEPTH][ALD], rb[DEPTH][BLD];
+    // (kRot) B has one register set: a stage's 24 KB of B are 6 pieces per thread, and two sets of them beside
+    // the 128 accumulators do not fit the 256 registers of two waves per SIMD.  The weights come from the L2,
+    // so chunk s + 1's B is loaded at the start of stage s and written to LDS beside its last column block.
+    constexpr int BSETS = kRot ? 1 : DEPTH;
+    floatx4 ra[DEPTH][ALD], rb[BSETS][BLD];
     // Straight-line staging: every call issues exactly ALD + BLD loads (an empty
     // view when `valid` is false, reads return zero) with no data-dependent branch,
     // so the compiler tracks vmcnt precisely and the LDS writes of one register
     // set wait only for that set's loads, not for the prefetch issued after them.
-    auto gload = [&](int set, int kc, int m0, int n0, bool valid) {
+    // what: 0 the stage's A and B, 1 A only, 2 B only (kRot)
+    auto gload = [&](int set, int kc, int m0, int n0, bool valid, int what = 0) {
         const int k0 = kc * BK;
         const int rows = valid ? min(BM, p.M - m0) : 0;
         const bool second = k0 >= p.K1;  // wave-uniform: A2 half of a virtual concat
@@ -221,7 +261,8 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
                                    : reinterpret_cast<const char*>(cA) + (int64_t)m0 * p.lda * ESA;
         const int ald = second ? p.lda2 : p.lda;
         const int ak = second ? k0 - p.K1 : k0;
-        if constexpr (AX6) {  // chunk kc, rows m0 .. m0 + rows - 1: 96 * rows contiguous bytes
+        if (what == 2) {
+        } else if constexpr (AX6) {  // chunk kc, rows m0 .. m0 + rows - 1: 96 * rows contiguous bytes
             const rsrc_t rA = make_view(reinterpret_cast<const float*>(reinterpret_cast<const char*>(cA) +
                                                                        ((int64_t)kc * p.lda + m0) * 96), rows * 96);
 #pragma unroll
@@ -231,12 +272,13 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
 #pragma unroll
         for (int q = 0; q < ALD; ++q) ra[set][q] = bload4(rA, second ? voA2[q] : voA[q], ak * ESA);
         }
+        if (what == 1) return;
         // MODE 2: chunk kc of the image is [ldb rows][48 bf16]; the tile's BN rows are 96 * BN contiguous bytes
         const int64_t bofs = MODE == 2 ? ((int64_t)kc * (BK / 16) * p.ldb + n0) * 96 : (int64_t)n0 * p.ldb * ESZB;
         const rsrc_t rB = make_view(reinterpret_cast<const float*>(reinterpret_cast<const char*>(cB) + bofs),
                                     valid ? (MODE == 2 ? ((BK / 16 - 1) * p.ldb + BN) * 96 : BN * p.ldb * ESZB) : 0);
 #pragma unroll
-        for (int q = 0; q < BLD; ++q) rb[set][q] = bload4(rB, voB[q], MODE == 2 ? 0 : k0 * ESZB);
+        for (int q = 0; q < BLD; ++q) rb[kRot ? 0 : set][q] = bload4(rB, voB[q], MODE == 2 ? 0 : k0 * ESZB);
     };
     // piece < 0: the whole stage; piece q < ALD: A row q only; piece ALD: B only
     auto lstore = [&](int set, int buf, int piece = -1) {
@@ -251,6 +293,13 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
             } else if constexpr (MODE == 2) {
                 bf16x4 x0, x1, x2;
                 split3(ra[set][q], x0, x1, x2);
+                if constexpr (kRot) {
+                    float* ar = sA + buf * BM * LS + (srow + q * RSTEP) * LS + rotA;
+                    *reinterpret_cast<bf16x4*>(ar) = x0;
+                    *reinterpret_cast<bf16x4*>(ar + BK / 2) = x1;
+                    *reinterpret_cast<bf16x4*>(ar + BK) = x2;
+                    continue;
+                }
                 *reinterpret_cast<bf16x4*>(a + q * RSTEP * LS) = x0;
                 *reinterpret_cast<bf16x4*>(a + q * RSTEP * LS + BK / 2) = x1;
                 *reinterpret_cast<bf16x4*>(a + q * RSTEP * LS + BK) = x2;
@@ -267,7 +316,7 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
             if constexpr (MODE == 2) {
                 const int idx = tid + q * NT;
                 if (BN * KCB % NT == 0 || idx < BN * KCB)  // wave-uniform (NT, BN*KCB multiples of 64)
-                    *reinterpret_cast<floatx4*>(sB + buf * BN * LS + ldsB[q]) = rb[set][q];
+                    *reinterpret_cast<floatx4*>(sB + buf * BN * LS + ldsB[q]) = rb[kRot ? 0 : set][q];
             } else {
                 *reinterpret_cast<floatx4*>(b + q * RSTEPB * LS) = rb[set][q];
             }
@@ -289,9 +338,12 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
         return ntiles;
     };
 
-    // pinned compute/staging segments: the 256x256 bf16x6 tile (one workgroup per CU, so no
-    // partner workgroup's MFMAs cover a trailing staging block)
-    constexpr bool kSeg = MODE == 2 && TM * TN >= 8 && TN > ALD && DEPTH == 2 && OCC == 1 && BK == 16;
+    // pinned compute/staging segments: the 64x128 wave tiles of the bf16x6 mode (the 256x256 tile has one
+    // workgroup per CU, so no partner workgroup's MFMAs cover a trailing staging block; the two-per-CU
+    // 128x256 tile has the same two waves per SIMD and keeps the structure)
+    constexpr bool kSeg = MODE == 2 && TM * TN >= 8 && TN > ALD && DEPTH == 2 && (OCC == 1 || kRot) && BK == 16;
+    // (kRot) fragment reads: logical piece 2 t + (lane >> 5) of row lane & 31 of a 32-row block
+    const int rotF = ((lane >> 5) ^ ((lane & 31) >> 3 & 1)) * 4;
     const int arow = wm * TM * 32 + (lane & 31);
     const int brow = wn * TN * 32 + (lane & 31);
     const int kofs = (BK / 2) * (lane >> 5);
@@ -323,6 +375,15 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
 
     int vt = next_valid(blockIdx.x);
     if (vt >= ntiles) return;
+    // measurement build only (-DCN_AB_TALL2_OFFSET=ticks of the 100 MHz clock): the second workgroup of each CU
+    // of the two-per-CU 128x256 tile starts late, so the partners' epilogues fall into each other's main loops
+    // from the first tile on (profiles/r7_ab.txt)
+    if constexpr (kRot && CN_AB_TALL2_OFFSET > 0) {
+        if (blockIdx.x >= gridDim.x / 2) {
+            const uint64_t t0 = wall_clock64();
+            while (wall_clock64() - t0 < (uint64_t)CN_AB_TALL2_OFFSET) __builtin_amdgcn_s_sleep(8);
+        }
+    }
     if constexpr (TBL > 0) {  // visible after the first tile's staging barrier
         const rsrc_t rbias = make_view(p.bias, kBias && p.bias ? cN * 4 : 0);
         const rsrc_t rcolv = make_view(p.colv, kColv && p.colv ? cN * 4 : 0);
@@ -403,13 +464,14 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
         // tile's are fetched during the current tile's last DEPTH chunks); see the end of the tile
         // loop for the asm re-definition (the sets enter the loop as asm-defined values on both paths)
 #pragma unroll
-        for (int d = 0; d < DEPTH; ++d) gload(d, d, tm * BM, tn * BN, true);
+        for (int d = 0; d < DEPTH; ++d) gload(d, d, tm * BM, tn * BN, true, kRot && d > 0 ? 1 : 0);
 #pragma unroll
         for (int d = 0; d < DEPTH; ++d) {
 #pragma unroll
             for (int q = 0; q < ALD; ++q) asm volatile("" : "+v"(ra[d][q]));
 #pragma unroll
-            for (int q = 0; q < BLD; ++q) asm volatile("" : "+v"(rb[d][q]));
+            for (int q = 0; q < BLD; ++q)
+                if (d < BSETS) asm volatile("" : "+v"(rb[d][q]));
         }
     }
     // (kDma) per-lane column-table values of the direct epilogues, n0 = 0
@@ -459,8 +521,8 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
         // handed to side() interleave with that block's MFMAs instead of trailing all of them)
         auto compute = [&](int cur, auto side) {
             if constexpr (MODE == 2) {
-                const float* a_base = sA + cur * BM * LS + arow * LS + 4 * (lane >> 5);
-                const float* b_base = sB + cur * BN * LS + brow * LS + 4 * (lane >> 5);
+                const float* a_base = sA + cur * BM * LS + arow * LS + (kRot ? rotF : 4 * (lane >> 5));
+                const float* b_base = sB + cur * BN * LS + brow * LS + (kRot ? rotF : 4 * (lane >> 5));
                 if constexpr (TM * TN >= 8) {
                     // 64x128 wave tiles: the B fragments of one column block at a time (12 VGPRs
                     // instead of 48 live); a single accumulation chain issues back to back
@@ -634,6 +696,22 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
                     const bool here = cn < nk;
                     // past this tile: chunk cn - nk of the next one, issued before this tile's
                     // epilogue stores, so the next tile's first DEPTH stagings never wait for them
+                    if constexpr (kRot) {
+                        // B's one set (free since the previous stage's last segment) takes chunk kc + j + 1, or
+                        // the next tile's chunk 0, which that tile's first staging writes again; issued before
+                        // A's loads of chunk kc + j + 2, so the wait for it leaves those in flight
+                        static_assert(kSeg, "the one-set B staging lives in the pinned segments");
+                        const int cb = kc + j + 1;
+                        const bool hb = cb < nk;
+                        gload(0, hb ? cb : 0, hb ? m0 : m_next, hb ? n0 : n_next, hb || has_next, 2);
+                        gload(j, here ? cn : cn - nk, here ? m0 : m_next, here ? n0 : n_next, here || has_next, 1);
+                        compute(j & 1, [&](int jj) {
+                            if (jj < ALD) lstore((j + 1) % DEPTH, (j + 1) & 1, jj);
+                            if (jj == TN - 1) lstore(0, (j + 1) & 1, ALD);
+                        });
+                        __syncthreads();
+                        continue;
+                    }
                     gload(j, here ? cn : cn - nk, here ? m0 : m_next, here ? n0 : n_next, here || has_next);
                     if constexpr (kSeg) {
                         // the next stage's staging (unconditional: after a tile's last chunk it
@@ -668,7 +746,8 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
 #pragma unroll
                 for (int q = 0; q < ALD; ++q) asm volatile("" : "+v"(ra[d][q]));
 #pragma unroll
-                for (int q = 0; q < BLD; ++q) asm volatile("" : "+v"(rb[d][q]));
+                for (int q = 0; q < BLD; ++q)
+                    if (d < BSETS) asm volatile("" : "+v"(rb[d][q]));
             }
         }
         // Epilogue: park the accumulator tile (or a slab of PROWS rows of it) in the
@@ -1172,8 +1251,10 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
         // epilogue issues at least TM * 8 * TN vector-memory operations per wave (one image dword per
         // row pair and column block), which the LDS-DMA ring's vmcnt(63) relies on (kEpiMinVmem;
         // tools/isa_check.py verifies it on the built ISA)
+        // (the bf16x6 mode has no bf16 images, host-checked: the two-per-CU 128x256 tile, at its register limit,
+        // carries no image-only variant)
         auto run_direct_plain = [&]() {
-            if (has_o0) {
+            if (has_o0 || kRot) {
                 if (has_b0) direct_plain(T1{}, T1{}); else direct_plain(T1{}, F0{});
             } else {
                 direct_plain(F0{}, T1{});
@@ -1181,7 +1262,7 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
         };
         auto run_direct_aux = [&]() {
             auto go = [&](auto spl) {
-                if (has_o0) {
+                if (has_o0 || kRot) {
                     if (has_b0) direct_aux(T1{}, T1{}, spl); else direct_aux(T1{}, F0{}, spl);
                 } else {
                     direct_aux(F0{}, T1{}, spl);
@@ -1665,18 +1746,23 @@ static int launch_linear_tile(const cn_linear_desc* d, LinearArgs& a, hipStream_
 //     read and split once), direct epilogues (STORE / SOFTPLUS / RELU / MUL incl. the split output /
 //     TANGENT / BWD_RELU / SOFTPLUS_HEAD) for 128 < N <= 256, K >= 128.  Main loop 316-320 us vs 374
 //     on 256x128; SOFTPLUS 445 vs 480-509, RELU 385 vs 408-420, MUL / TANGENT 443-451 vs 470.
+//   * TALL2 128x256 (2 / CU), 4 waves of 64x128, 16-deep stages on unpadded 96-byte rows (72 KB), B staged from one
+//     register set: the partner workgroup's main loop runs under the epilogue.  MUL 409 vs 431 on SQ, TANGENT 407 vs
+//     432, BWD_RELU 406 vs 427, BWD_SOFTPLUS 546 vs 582 on T128 (593 on SQ); RELU 349 vs 352, SOFTPLUS 372 vs 369,
+//     STORE 371 vs 363: the aux-reading classes take it (M > 65,536), C2 step 27.12 -> 26.74 ms.  tile = 3 forces it.
 //   * TALL 128x256 (1 / CU): SOFTPLUS_HEAD / MUL / TANGENT where SQ does not apply.
 //   * WIDE 256x128 (1 / CU, 32-deep): STORE / SOFTPLUS / RELU / MUL / TANGENT at K % 64 == 0.
-//   * T128 128x128 (2 / CU): BWD_SOFTPLUS (its three aux streams need the partner workgroup's main
-//     loop to hide: 614 vs 667 us on SQ), first layers (K < 128), edge shapes.
+//   * T128 128x128 (2 / CU): first layers (K < 128), edge shapes, BWD_SOFTPLUS at M <= 65,536 (its three aux
+//     streams need the partner workgroup's main loop to hide: 614 vs 667 us on SQ).
 //   bf16 (config C3) tiles: SQ 256x256 (1 / CU, 32-deep) for 128 < N <= 256, else 128x128 / 128x64.
-enum LinearTile { LT_BF_SQ, LT_BF_T0, LT_BF_T1, LT_X6_SQ, LT_X6_TALL, LT_X6_WIDE, LT_X6_T128, LT_X6_T1, LT_F_T0_D2,
-                  LT_F_T0_D1, LT_F_T1_D2, LT_F_T1_D1 };
+enum LinearTile { LT_BF_SQ, LT_BF_T0, LT_BF_T1, LT_X6_SQ, LT_X6_TALL2, LT_X6_TALL, LT_X6_WIDE, LT_X6_T128, LT_X6_T1, LT_F_T0_D2,
+                  LT_F_T0_D1, LT_F_T1_D2, LT_F_T1_D1, LT_NONE /* a forced tile that is not built for the descriptor */ };
 #define CN_LINEAR_TILES(X)                 \
     X(LT_BF_SQ, 4, 2, 2, 4, 32, 1, 2, 1)   \
     X(LT_BF_T0, 2, 2, 2, 2, 64, 2, 1, 1)   \
     X(LT_BF_T1, 4, 1, 1, 2, 64, 2, 1, 1)   \
     X(LT_X6_SQ, 4, 2, 2, 4, 16, 1, 2, 2)   \
+    X(LT_X6_TALL2, 2, 2, 2, 4, 16, 2, 2, 2) \
     X(LT_X6_TALL, 4, 2, 1, 4, 32, 1, 2, 2) \
     X(LT_X6_WIDE, 4, 2, 2, 2, 32, 1, 2, 2) \
     X(LT_X6_T128, 2, 2, 2, 2, 16, 2, 2, 2) \
@@ -1686,10 +1772,33 @@ enum LinearTile { LT_BF_SQ, LT_BF_T0, LT_BF_T1, LT_X6_SQ, LT_X6_TALL, LT_X6_WIDE
     X(LT_F_T1_D2, 4, 1, 1, 2, 32, 2, 2, 0) \
     X(LT_F_T1_D1, 4, 1, 1, 2, 32, 2, 1, 0)
 
-// measurement build only (-DCN_AB_X6_BWD_SQ=1, profiles/r5_ab.txt): bf16x6 BWD_SOFTPLUS on the 256x256 tile
-#ifndef CN_AB_X6_BWD_SQ
-#define CN_AB_X6_BWD_SQ 0
+// The two-per-CU 128x256 bf16x6 tile is chosen (tile == 0) for the classes in CN_X6_TALL2_CLASSES, from an M at
+// which each of its 2 x CUs persistent workgroups has more than one 128-row tile on a 256-CU part (a
+// constant: cn_linear_kernel_name touches no device): there is no second tile to overlap an epilogue
+// with below it.
+constexpr int kTall2MinM = 2 * 256 * 128;
+// bit e: epilogue class e takes the tile.  The classes that gained in the step A/B (profiles/r7_ab.txt, DESIGN.md
+// §3.1): the aux-reading epilogues.  RELU (349 vs 352 us per launch, equal in the step) and STORE (371 vs 363 us)
+// stay on the 256x256 tile, like the pinned SOFTPLUS (372 vs 369 us).
+#ifndef CN_X6_TALL2_CLASSES
+#define CN_X6_TALL2_CLASSES ((1u << CN_EPI_BWD_SOFTPLUS) | (1u << CN_EPI_MUL) | (1u << CN_EPI_TANGENT) | (1u << CN_EPI_BWD_RELU))
 #endif
+// measurement build only (-DCN_AB_TALL2_ENV=1): the class mask from the environment (COPENERF_TALL2_CLASSES), so one
+// library serves a step A/B of every class
+#ifndef CN_AB_TALL2_ENV
+#define CN_AB_TALL2_ENV 0
+#endif
+static unsigned tall2_classes() {
+#if CN_AB_TALL2_ENV
+    static const unsigned m = [] {
+        const char* e = getenv("COPENERF_TALL2_CLASSES");
+        return e ? (unsigned)strtoul(e, nullptr, 0) : (unsigned)(CN_X6_TALL2_CLASSES);
+    }();
+    return m;
+#else
+    return CN_X6_TALL2_CLASSES;
+#endif
+}
 
 // bf16x6 launches of at most this many rows (the sampler's up-sampling queries: 65,536 rows = one 256x256
 // tile per CU, nothing to overlap an epilogue with) take the two-per-CU tiles: SOFTPLUS the 128x128 one,
@@ -1712,13 +1821,20 @@ static LinearTile choose_linear_tile(const cn_linear_desc* d) {
     if (d->mfma_dtype == CN_MFMA_F32_BF16X6) {
         if (d->tile == 1) return LT_X6_T1;
         if (d->tile == 2) return LT_X6_T128;
+        // the 64x128 wave tiles: one tile spans every column, no rank-1 term, no edge path
+        const bool wave_wide = d->N > 128 && d->N <= 256 && !d->rowv && d->K % 32 == 0 && d->ldb >= 256;
+        if (d->tile == 3) return wave_wide ? LT_X6_TALL2 : LT_NONE;
+        if (d->tile == 4) return wave_wide ? LT_X6_SQ : LT_NONE;
         if (d->M <= CN_X6_SMALL_M && wide_n && d->K % 64 == 0 && longk && d->ldb >= 256) {
             if (e == CN_EPI_SOFTPLUS) return LT_X6_T128;
             if (head) return LT_X6_TALL;
         }
         // (BWD_SOFTPLUS on the 256x256 tile: re-measured in round 4 with the branch-free epilogue, equal or
         // slower -- 4.25 vs 4.17 ms per C2 step, profiles/r4_ab.txt r4m)
-        if (wide_n && d->K % 32 == 0 && d->ldb >= 256 && (e != CN_EPI_BWD_SOFTPLUS || CN_AB_X6_BWD_SQ) && (longk || head))
+        if (wide_n && d->K % 32 == 0 && d->ldb >= 256 && longk && d->M > kTall2MinM && (tall2_classes() >> e & 1) &&
+            !(e == CN_EPI_MUL && d->out_split && d->nsplit < d->N))
+            return LT_X6_TALL2;
+        if (wide_n && d->K % 32 == 0 && d->ldb >= 256 && e != CN_EPI_BWD_SOFTPLUS && (longk || head))
             return LT_X6_SQ;
         const bool tall = e == CN_EPI_MUL || e == CN_EPI_TANGENT || head;
         if (d->K % 64 == 0 && tall && d->N > 128 && d->ldb >= 256 && (longk || head)) return LT_X6_TALL;
@@ -1744,7 +1860,8 @@ static int linear_plan(const cn_linear_desc* d, LinearArgs& a) {
     const bool bf = d->mfma_dtype == CN_MFMA_BF16;
     const bool x6 = d->mfma_dtype == CN_MFMA_F32_BF16X6;
     CN_REQUIRE(d->K % (bf ? 64 : 32) == 0, CN_ERR_SHAPE, "cn_linear: K=%d must be a multiple of %d", d->K, bf ? 64 : 32);
-    CN_REQUIRE(d->tile >= 0 && d->tile <= 2, CN_ERR_ARG, "cn_linear: bad tile %d", d->tile);
+    CN_REQUIRE(d->tile >= 0 && d->tile <= 4, CN_ERR_ARG, "cn_linear: bad tile %d", d->tile);
+    CN_REQUIRE(d->tile <= 2 || x6, CN_ERR_UNSUPPORTED, "cn_linear: tile %d is a bf16x6 tile", d->tile);
     if (x6 && d->a_bf16 && CN_AB_X6_AIMG) {  // (measurement build) A as a bf16x6 term image, rows = lda
         CN_REQUIRE(!d->A2 && !d->aux0_bf16 && !d->aux12_bf16 && !d->out0_b && !d->out1_b && d->lda >= d->M &&
                        al16(d->A) && choose_linear_tile(d) == LT_X6_SQ,
@@ -1871,13 +1988,17 @@ extern "C" int cn_linear(const cn_linear_desc* d, cn_stream_t stream) {
         case T: return launch_linear_tile<WM, WN, TM, TN, BK, OCC, DEPTH, MODE>(d, a, s);
         CN_LINEAR_TILES(CN_TILE_CASE)
 #undef CN_TILE_CASE
+        case LT_NONE: break;
     }
-    set_error("cn_linear: no tile");
+    set_error("cn_linear: tile %d is not built for this descriptor (128 < N <= 256, no rowv, K %% 32 == 0, ldb >= 256)", d->tile);
     return CN_ERR_UNSUPPORTED;
 }
 
 extern "C" int cn_linear_kernel_name(const cn_linear_desc* d, char* buf, int32_t len) {
     CN_REQUIRE(d && buf && len > 0, CN_ERR_ARG, "cn_linear_kernel_name: null desc / buffer");
+    CN_REQUIRE(d->tile >= 0 && d->tile <= 4, CN_ERR_ARG, "cn_linear_kernel_name: bad tile %d", d->tile);
+    CN_REQUIRE(d->tile <= 2 || d->mfma_dtype == CN_MFMA_F32_BF16X6, CN_ERR_UNSUPPORTED,
+               "cn_linear_kernel_name: tile %d is a bf16x6 tile", d->tile);
     const char* args = "";
     int mode = 0;
     switch (choose_linear_tile(d)) {
@@ -1885,6 +2006,9 @@ extern "C" int cn_linear_kernel_name(const cn_linear_desc* d, char* buf, int32_t
         case T: args = #WM ", " #WN ", " #TM ", " #TN ", " #BK ", " #OCC ", " #DEPTH; mode = linear_mode_bits(d, MODE); break;
         CN_LINEAR_TILES(CN_TILE_NAME)
 #undef CN_TILE_NAME
+        case LT_NONE:
+            set_error("cn_linear_kernel_name: tile %d is not built for this descriptor", d->tile);
+            return CN_ERR_UNSUPPORTED;
     }
     const int n = snprintf(buf, (size_t)len, "void cn::linear_kernel<%s, %d, %s, %d>(cn::LinearArgs)", args,
                            d->epilogue, d->rowv && (mode & 8) == 0 ? "true" : "false", mode);

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CN_ABI_VERSION 21
+#define CN_ABI_VERSION 22
 
 typedef void* cn_stream_t; /* hipStream_t */
 
@@ -99,7 +99,10 @@ typedef struct cn_linear_desc {
     int32_t nzero, nsplit;
     int32_t epilogue;    /* cn_epilogue */
     int32_t tile;        /* 0: the library's tile choice (up to 256x256), 1: 128x64, 2: 128x128 only
-                            (tests compare the tiles: every tile gives the same bits) */
+                            (tests compare the tiles: every tile gives the same bits); bf16x6 only
+                            (ABI v22): 3 the two-per-CU 128x256 tile, 4 the one-per-CU 256x256 tile,
+                            both for 128 < N <= 256, no rowv, ldb >= 256 (else CN_ERR_UNSUPPORTED);
+                            above 4: CN_ERR_ARG */
     float adiv, odiv;    /* divisors applied to A·Bᵀ and to the activation (0 means 1),
                             applied as multiplies by their fp32 reciprocals */
     float beta, threshold; /* Softplus(beta, threshold) of neus_fields.py:266 */

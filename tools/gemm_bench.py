@@ -24,6 +24,9 @@ def timeit(fn, iters=20):
 
 
 ONLY = os.environ.get("ONLY", "")  # substring filter on the variant names
+# cn_linear_desc.tile of the bf16x6 launches, comma-separated (0: the library's choice, 2: 128x128, 3: the
+# two-per-CU 128x256 tile, 4: 256x256): TILE=0,2,3,4 times every epilogue on each in one process
+TILES = [int(t) for t in os.environ.get("TILE", "0").split(",")]
 
 
 def bench(res, key, fn, div=1):
@@ -99,8 +102,11 @@ def main():
                           ("bwd_softplus", ops.EPI_BWD_SOFTPLUS, so),
                           # (stream-count probes: aux2 = aux1 -- two distinct aux streams; no aux1 / aux2 -- one)
                           ("bwd_softplus_2str", ops.EPI_BWD_SOFTPLUS, dict(so, aux2=aux1)),
-                          ("bwd_softplus_1str", ops.EPI_BWD_SOFTPLUS, sg)):
-        bench(res, "cn_linear x6 " + name, lambda: ops.linear(A, Bs, N, K, o0, epi, **kw))
+                          ("bwd_softplus_1str", ops.EPI_BWD_SOFTPLUS, sg),
+                          ("bwd_relu", ops.EPI_BWD_RELU, dict(aux0=aux1))):
+        for t in TILES:
+            bench(res, "cn_linear x6 " + name + (f" tile{t}" if t else ""),
+                  lambda: ops.linear(A, Bs, N, K, o0, epi, tile=t or None, **kw))
     if os.environ.get("X6_AIMG"):  # (a -DCN_AB_X6_AIMG=1 library) A as a bf16x6 term image, no split while staging
         As = ops.split_bf16x3(A)  # [K/16, M, 48]: the layout of B's images
         for name, epi, kw in (("store", ops.EPI_STORE, dict(bias=bias)),

@@ -29,7 +29,9 @@ def main(fetch_csv, write_csv, out):
         wb = 1024.0 * sum(v for v, _ in wv) / len(wv)
         kernels[name] = {"launches": len(fv), "fetch_bytes_per_launch": fb, "write_bytes_per_launch": wb,
                          "hbm_bytes_per_launch": fb + wb}
-    json.dump({"source": [fetch_csv, write_csv], "correction": "fetch = 2 * FETCH_SIZE * 1024 (gfx950), "
+    # (the round's own directory names, not the absolute path of the box the passes ran on)
+    rel = lambda p: "/".join(p.replace("\\", "/").split("/")[-3:])
+    json.dump({"source": [rel(fetch_csv), rel(write_csv)], "correction": "fetch = 2 * FETCH_SIZE * 1024 (gfx950), "
                "write = WRITE_SIZE * 1024", "kernels": kernels}, open(out, "w"), indent=1)
     for name, k in sorted(kernels.items(), key=lambda kv: -kv[1]["hbm_bytes_per_launch"] * kv[1]["launches"])[:12]:
         print(f"{k['hbm_bytes_per_launch']/1e6:10.1f} MB/launch x{k['launches']:4d}  fetch {k['fetch_bytes_per_launch']/1e6:9.1f}"
