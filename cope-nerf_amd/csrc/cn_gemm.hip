@@ -20,7 +20,6 @@
 
 #include <algorithm>
 #include <type_traits>
-#include <cstdlib>
 
 namespace cn {
 
@@ -83,12 +82,6 @@ struct LinearArgs {
 //         and aux2 are bf16 images.
 constexpr int kTblCols = 512;  // widest N with a bias / colv (the LDS column table)
 
-#ifndef CN_AB_TALL2_OFFSET
-#define CN_AB_TALL2_OFFSET 0  // (measurement) start delay of each CU's second 128x256 workgroup
-#endif
-#ifndef CN_DMA_A_NT
-#define CN_DMA_A_NT 0  // 1: the LDS-DMA ring's A chunks loaded non-temporally (measured slower: a 32-deep chunk is half a 128-byte line; profiles/r6_ab.txt r6x)
-#endif
 template <int WM, int WN, int TM, int TN, int BK, int OCC, int DEPTH, int EPI, bool ROWV, int MODE_>
 __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel(LinearArgs p) {
     constexpr int MODE = MODE_ & 3;         // the GEMM mode (0 fp32, 1 bf16, 2 bf16x6)
@@ -99,10 +92,6 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
                                                 EPI == CN_EPI_BWD_SOFTPLUS);
     constexpr bool AUX12B = (MODE_ & 8) != 0 && EPI == CN_EPI_BWD_SOFTPLUS;
     static_assert(!ABF || MODE == 1, "bf16 A images only in the bf16 MFMA mode");
-    // MODE_ bit 4 (MODE 2, measurement build CN_AB_X6_AIMG): A arrives as a bf16x6 term image in B's chunk-major
-    // format ([K/16][lda rows][3 terms][16], lda = the image's rows), staged like B: no split
-    constexpr bool AX6 = (MODE_ & 16) != 0;
-    static_assert(!AX6 || (MODE == 2 && BK == 16), "bf16x6 A images: 16-deep stages of the bf16x6 mode");
     constexpr int NT = 64 * WM * WN;
     const float* const cA = p.A;
     const float* const cB = p.B;
@@ -132,7 +121,7 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
     // {8, 14, 4, 10}, 16-19 {0, 6, 12, 2} (t = 0), rows 8-11 {0, 6, 12, 2}, 28-31 {8, 14, 4, 10} (t = 1): the same
     // two sets.  Lanes 32-63 read the other k half (c ^ 1) of the same rows: the same argument.  Conflict-free
     // for every c, on the A and the B fragments alike.
-    constexpr bool kRot = MODE == 2 && BK == 16 && OCC == 2 && TM * TN >= 8 && (MODE_ & 16) == 0;
+    constexpr bool kRot = MODE == 2 && BK == 16 && OCC == 2 && TM * TN >= 8;
     constexpr int LS = kRot ? 24 : (BF ? NPL * BK / 2 : BK) + (MODE == 2 && BK == 16 ? 12 : 4);
     constexpr int EPA = ABF ? 8 : 4;             // A elements per 16-byte staging piece
     constexpr int ESA = ABF ? 2 : 4;             // bytes per A element
@@ -143,7 +132,7 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
     // modes 0/1: B rows tid/KCB + q*RSTEPB; mode 2 (6 pieces per row): piece tid + q*NT
     constexpr int RSTEPB = MODE == 2 ? 1 : NT / KCB;
     static_assert(BM % RSTEP == 0 && (MODE == 2 || (NT % KCB == 0 && BN % RSTEPB == 0)), "tile/thread mismatch");
-    constexpr int ALD = AX6 ? (BM * 6 + NT - 1) / NT : BM / RSTEP;  // (AX6: 16-byte pieces like B's)
+    constexpr int ALD = BM / RSTEP;
     constexpr int BLD = MODE == 2 ? (BN * KCB + NT - 1) / NT : BN / RSTEPB;
     constexpr int ESZB = BF ? 2 : 4;             // bytes per B element
     constexpr int PIECES_PL = BK / 8;            // MODE 2: 16-byte pieces per plane of a staged row
@@ -198,18 +187,10 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
     const int srowb = tid / KCB, scb = tid % KCB;
     int voA[ALD], voA2[ALD], voB[BLD];  // byte offsets of the staged rows (range-checked)
     int ldsB[BLD];                      // MODE 2: LDS dword offset of B piece q within a buffer
-    int ldsA[AX6 ? ALD : 1];            // (AX6) LDS dword offset of A piece q, as ldsB
 #pragma unroll
     for (int q = 0; q < ALD; ++q) {
-        if constexpr (AX6) {  // piece idx: row w / 6, term (w % 6) / 2, k half w % 2 of the tile's contiguous chunk
-            const int w = tid + q * NT;
-            voA[q] = w < BM * 6 ? w * 16 : 0;
-            voA2[q] = 0;
-            ldsA[q] = (w / 6) * LS + ((w % 6) >> 1) * (BK / 2) + 4 * (w & 1);
-        } else {
-            voA[q] = ((srow + q * RSTEP) * p.lda + sc4 * EPA) * ESA;
-            voA2[q] = ((srow + q * RSTEP) * p.lda2 + sc4 * EPA) * ESA;
-        }
+        voA[q] = ((srow + q * RSTEP) * p.lda + sc4 * EPA) * ESA;
+        voA2[q] = ((srow + q * RSTEP) * p.lda2 + sc4 * EPA) * ESA;
     }
 #pragma unroll
     for (int q = 0; q < BLD; ++q) {
@@ -261,16 +242,10 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
                                    : reinterpret_cast<const char*>(cA) + (int64_t)m0 * p.lda * ESA;
         const int ald = second ? p.lda2 : p.lda;
         const int ak = second ? k0 - p.K1 : k0;
-        if (what == 2) {
-        } else if constexpr (AX6) {  // chunk kc, rows m0 .. m0 + rows - 1: 96 * rows contiguous bytes
-            const rsrc_t rA = make_view(reinterpret_cast<const float*>(reinterpret_cast<const char*>(cA) +
-                                                                       ((int64_t)kc * p.lda + m0) * 96), rows * 96);
+        if (what != 2) {
+            const rsrc_t rA = make_view(reinterpret_cast<const float*>(abase), rows * ald * ESA);
 #pragma unroll
-            for (int q = 0; q < ALD; ++q) ra[set][q] = bload4(rA, voA[q], 0);
-        } else {
-        const rsrc_t rA = make_view(reinterpret_cast<const float*>(abase), rows * ald * ESA);
-#pragma unroll
-        for (int q = 0; q < ALD; ++q) ra[set][q] = bload4(rA, second ? voA2[q] : voA[q], ak * ESA);
+            for (int q = 0; q < ALD; ++q) ra[set][q] = bload4(rA, second ? voA2[q] : voA[q], ak * ESA);
         }
         if (what == 1) return;
         // MODE 2: chunk kc of the image is [ldb rows][48 bf16]; the tile's BN rows are 96 * BN contiguous bytes
@@ -287,10 +262,7 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
 #pragma unroll
         for (int q = 0; q < ALD; ++q) {
             if (piece >= 0 && piece != q) continue;
-            if constexpr (AX6) {
-                if (BM * 6 % NT == 0 || tid + q * NT < BM * 6)  // wave-uniform
-                    *reinterpret_cast<floatx4*>(sA + buf * BM * LS + ldsA[q]) = ra[set][q];
-            } else if constexpr (MODE == 2) {
+            if constexpr (MODE == 2) {
                 bf16x4 x0, x1, x2;
                 split3(ra[set][q], x0, x1, x2);
                 if constexpr (kRot) {
@@ -375,15 +347,6 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
 
     int vt = next_valid(blockIdx.x);
     if (vt >= ntiles) return;
-    // measurement build only (-DCN_AB_TALL2_OFFSET=ticks of the 100 MHz clock): the second workgroup of each CU
-    // of the two-per-CU 128x256 tile starts late, so the partners' epilogues fall into each other's main loops
-    // from the first tile on (profiles/r7_ab.txt)
-    if constexpr (kRot && CN_AB_TALL2_OFFSET > 0) {
-        if (blockIdx.x >= gridDim.x / 2) {
-            const uint64_t t0 = wall_clock64();
-            while (wall_clock64() - t0 < (uint64_t)CN_AB_TALL2_OFFSET) __builtin_amdgcn_s_sleep(8);
-        }
-    }
     if constexpr (TBL > 0) {  // visible after the first tile's staging barrier
         const rsrc_t rbias = make_view(p.bias, kBias && p.bias ? cN * 4 : 0);
         const rsrc_t rcolv = make_view(p.colv, kColv && p.colv ? cN * 4 : 0);
@@ -430,18 +393,12 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
         const rsrc_t v = __builtin_amdgcn_make_buffer_rsrc(ufirst(base), 0, __builtin_amdgcn_readfirstlane(bytes),
                                                            0x00020000);
         char* dst = reinterpret_cast<char*>(smem) + slot * DSTAGE + (dsb ? DSIDEA : 0) + (dwave & 3) * 64 * DROWB;
-        // (A, read once per tile, non-temporally with CN_DMA_A_NT; the weights stay cached: every workgroup reads them)
-        if (CN_DMA_A_NT && !dsb) {
+        // (default cache policy for A too: a 32-deep chunk is half a 128-byte line, and non-temporal loads
+        // measured slower, profiles/r6_ab.txt r6x)
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(v, (__attribute__((address_space(3))) void*)(dst + j * 1024), 16,
-                                                         (drow + 16 * j) * ld * 2 + (kk + dch * 8) * 2, 0, 0, 2);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(v, (__attribute__((address_space(3))) void*)(dst + j * 1024), 16,
-                                                         (drow + 16 * j) * ld * 2 + (kk + dch * 8) * 2, 0, 0, 0);
-        }
+        for (int j = 0; j < 4; ++j)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(v, (__attribute__((address_space(3))) void*)(dst + j * 1024), 16,
+                                                     (drow + 16 * j) * ld * 2 + (kk + dch * 8) * 2, 0, 0, 0);
     };
     // MFMA operand reads: lane l's row (l & 31) of each 32-row block, 16-byte chunk 2 ks + (l >> 5)
     // at its swizzled place ((row >> 2) & 3 = ((l & 31) >> 2) & 3: the blocks start at multiples of 32)
@@ -1012,7 +969,7 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
         auto bimg_pair = [&](const TileView& t, int rowi, int vb, float o_r, float o_r1, unsigned sel) {
             const unsigned own = pack_b16x2(o_r, o_r1);
             const unsigned recv = __builtin_amdgcn_mov_dpp(own, 0xB1, 0xF, 0xF, true);  // lane ^ 1
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_amdgcn_perm(recv, own, sel), view_at(t, rowi), vb, 0, CN_EPI_AUX);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_amdgcn_perm(recv, own, sel), view_at(t, rowi), vb, 0, kEpiPolicy);
         };
         // The direct epilogues take the wave-uniform choices (fp32 out0 stored, bf16 image of it, MUL's
         // split output) as template flags: as branches inside the element loops they left the
@@ -1389,35 +1346,24 @@ __global__ void __launch_bounds__(256) scale_cols_kernel(int M, int N4, const fl
 
 // 4 values at element offset i of an fp32 output, or of its bf16 operand image (ob)
 // four consecutive values of a row: fp32, or (B) a bf16 operand image widened
+// (the elementwise adjoint's rows are read and written once: non-temporally, profiles/r6_ab.txt r6w)
 template <bool B>
-#ifndef CN_STREAM_NT
-#define CN_STREAM_NT 1  // the elementwise adjoint's rows read / written non-temporally (profiles/r6_ab.txt r6w)
-#endif
 __device__ __forceinline__ floatx4 load_row4(const void* p, int64_t i) {
     if constexpr (B) {
-        const u32x2_t* a = reinterpret_cast<const u32x2_t*>(static_cast<const bf16_t*>(p) + i);
-        const u32x2_t w = CN_STREAM_NT ? __builtin_nontemporal_load(a) : *a;
+        const u32x2 w = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(static_cast<const bf16_t*>(p) + i));
         return floatx4{__builtin_bit_cast(float, w[0] << 16), __builtin_bit_cast(float, w[0] & 0xffff0000u),
                        __builtin_bit_cast(float, w[1] << 16), __builtin_bit_cast(float, w[1] & 0xffff0000u)};
     } else {
-        const floatx4* a = reinterpret_cast<const floatx4*>(static_cast<const float*>(p) + i);
-        return CN_STREAM_NT ? __builtin_nontemporal_load(a) : *a;
+        return __builtin_nontemporal_load(reinterpret_cast<const floatx4*>(static_cast<const float*>(p) + i));
     }
 }
 __device__ __forceinline__ void store_row4(void* out, bool ob, int64_t i, floatx4 v) {
     if (ob) {
         bf16x4* a = reinterpret_cast<bf16x4*>(static_cast<bf16_t*>(out) + i);
         const bf16x4 b = __builtin_convertvector(v, bf16x4);
-        if (CN_STREAM_NT)
-            __builtin_nontemporal_store(b, a);
-        else
-            *a = b;
+        __builtin_nontemporal_store(b, a);
     } else {
-        floatx4* a = reinterpret_cast<floatx4*>(static_cast<float*>(out) + i);
-        if (CN_STREAM_NT)
-            __builtin_nontemporal_store(v, a);
-        else
-            *a = v;
+        __builtin_nontemporal_store(v, reinterpret_cast<floatx4*>(static_cast<float*>(out) + i));
     }
 }
 
@@ -1711,21 +1657,11 @@ static int launch_linear_tile_m(const cn_linear_desc* d, LinearArgs& a, hipStrea
 // The template MODE_ of a descriptor on a tile of GEMM mode MODE: + 4 for bf16 A images, + 8 for a
 // bf16 aux0 (MODE 1 only).
 static int linear_mode_bits(const cn_linear_desc* d, int mode) {
-    if (mode == 2) return mode + (d->a_bf16 ? 16 : 0);  // (CN_AB_X6_AIMG) a bf16x6 term image of A
     return mode == 1 ? mode + (d->a_bf16 ? 4 : 0) + (d->aux0_bf16 || d->aux12_bf16 ? 8 : 0) : mode;
 }
 
-// measurement build only (-DCN_AB_X6_AIMG=1, profiles/r6_ab.txt): cn_linear reads A as a bf16x6 term image on the
-// 256x256 tile (a_bf16 set with CN_MFMA_F32_BF16X6; the layout of split_bf16x3's B images)
-#ifndef CN_AB_X6_AIMG
-#define CN_AB_X6_AIMG 0
-#endif
-
 template <int WM, int WN, int TM, int TN, int BK, int OCC, int DEPTH, int MODE = 0>
 static int launch_linear_tile(const cn_linear_desc* d, LinearArgs& a, hipStream_t s) {
-    if constexpr (MODE == 2 && CN_AB_X6_AIMG && BK == 16 && TM * TN >= 8) {
-        if (linear_mode_bits(d, MODE) == 18) return launch_linear_tile_m<WM, WN, TM, TN, BK, OCC, DEPTH, 18>(d, a, s);
-    }
     if constexpr (MODE == 1) {
         switch (linear_mode_bits(d, MODE)) {
             case 5: return launch_linear_tile_m<WM, WN, TM, TN, BK, OCC, DEPTH, 5>(d, a, s);
@@ -1772,7 +1708,7 @@ enum LinearTile { LT_BF_SQ, LT_BF_T0, LT_BF_T1, LT_X6_SQ, LT_X6_TALL2, LT_X6_TAL
     X(LT_F_T1_D2, 4, 1, 1, 2, 32, 2, 2, 0) \
     X(LT_F_T1_D1, 4, 1, 1, 2, 32, 2, 1, 0)
 
-// The two-per-CU 128x256 bf16x6 tile is chosen (tile == 0) for the classes in CN_X6_TALL2_CLASSES, from an M at
+// The two-per-CU 128x256 bf16x6 tile is chosen (tile == 0) for the classes in kTall2Classes, from an M at
 // which each of its 2 x CUs persistent workgroups has more than one 128-row tile on a 256-CU part (a
 // constant: cn_linear_kernel_name touches no device): there is no second tile to overlap an epilogue
 // with below it.
@@ -1780,32 +1716,7 @@ constexpr int kTall2MinM = 2 * 256 * 128;
 // bit e: epilogue class e takes the tile.  The classes that gained in the step A/B (profiles/r7_ab.txt, DESIGN.md
 // §3.1): the aux-reading epilogues.  RELU (349 vs 352 us per launch, equal in the step) and STORE (371 vs 363 us)
 // stay on the 256x256 tile, like the pinned SOFTPLUS (372 vs 369 us).
-#ifndef CN_X6_TALL2_CLASSES
-#define CN_X6_TALL2_CLASSES ((1u << CN_EPI_BWD_SOFTPLUS) | (1u << CN_EPI_MUL) | (1u << CN_EPI_TANGENT) | (1u << CN_EPI_BWD_RELU))
-#endif
-// measurement build only (-DCN_AB_TALL2_ENV=1): the class mask from the environment (COPENERF_TALL2_CLASSES), so one
-// library serves a step A/B of every class
-#ifndef CN_AB_TALL2_ENV
-#define CN_AB_TALL2_ENV 0
-#endif
-static unsigned tall2_classes() {
-#if CN_AB_TALL2_ENV
-    static const unsigned m = [] {
-        const char* e = getenv("COPENERF_TALL2_CLASSES");
-        return e ? (unsigned)strtoul(e, nullptr, 0) : (unsigned)(CN_X6_TALL2_CLASSES);
-    }();
-    return m;
-#else
-    return CN_X6_TALL2_CLASSES;
-#endif
-}
-
-// bf16x6 launches of at most this many rows (the sampler's up-sampling queries: 65,536 rows = one 256x256
-// tile per CU, nothing to overlap an epilogue with) take the two-per-CU tiles: SOFTPLUS the 128x128 one,
-// SOFTPLUS_HEAD the 128x256 one.  0: off (measurement switch, profiles/r6_ab.txt)
-#ifndef CN_X6_SMALL_M
-#define CN_X6_SMALL_M 0
-#endif
+constexpr unsigned kTall2Classes = (1u << CN_EPI_BWD_SOFTPLUS) | (1u << CN_EPI_MUL) | (1u << CN_EPI_TANGENT) | (1u << CN_EPI_BWD_RELU);
 
 static LinearTile choose_linear_tile(const cn_linear_desc* d) {
     const int e = d->epilogue;
@@ -1825,17 +1736,14 @@ static LinearTile choose_linear_tile(const cn_linear_desc* d) {
         const bool wave_wide = d->N > 128 && d->N <= 256 && !d->rowv && d->K % 32 == 0 && d->ldb >= 256;
         if (d->tile == 3) return wave_wide ? LT_X6_TALL2 : LT_NONE;
         if (d->tile == 4) return wave_wide ? LT_X6_SQ : LT_NONE;
-        if (d->M <= CN_X6_SMALL_M && wide_n && d->K % 64 == 0 && longk && d->ldb >= 256) {
-            if (e == CN_EPI_SOFTPLUS) return LT_X6_T128;
-            if (head) return LT_X6_TALL;
+        // (the library's choice from here: tile == 0, both callers check 0 <= tile <= 4)
+        if (wave_wide) {
+            if (longk && d->M > kTall2MinM && (kTall2Classes >> e & 1) && !(e == CN_EPI_MUL && d->out_split && d->nsplit < d->N))
+                return LT_X6_TALL2;
+            // (BWD_SOFTPLUS on the 256x256 tile: re-measured in round 4 with the branch-free epilogue, equal or
+            // slower -- 4.25 vs 4.17 ms per C2 step, profiles/r4_ab.txt r4m)
+            if (e != CN_EPI_BWD_SOFTPLUS && (longk || head)) return LT_X6_SQ;
         }
-        // (BWD_SOFTPLUS on the 256x256 tile: re-measured in round 4 with the branch-free epilogue, equal or
-        // slower -- 4.25 vs 4.17 ms per C2 step, profiles/r4_ab.txt r4m)
-        if (wide_n && d->K % 32 == 0 && d->ldb >= 256 && longk && d->M > kTall2MinM && (tall2_classes() >> e & 1) &&
-            !(e == CN_EPI_MUL && d->out_split && d->nsplit < d->N))
-            return LT_X6_TALL2;
-        if (wide_n && d->K % 32 == 0 && d->ldb >= 256 && e != CN_EPI_BWD_SOFTPLUS && (longk || head))
-            return LT_X6_SQ;
         const bool tall = e == CN_EPI_MUL || e == CN_EPI_TANGENT || head;
         if (d->K % 64 == 0 && tall && d->N > 128 && d->ldb >= 256 && (longk || head)) return LT_X6_TALL;
         // (an aux-reading epilogue with one workgroup per CU no longer overlaps a partner's main loop)
@@ -1862,11 +1770,7 @@ static int linear_plan(const cn_linear_desc* d, LinearArgs& a) {
     CN_REQUIRE(d->K % (bf ? 64 : 32) == 0, CN_ERR_SHAPE, "cn_linear: K=%d must be a multiple of %d", d->K, bf ? 64 : 32);
     CN_REQUIRE(d->tile >= 0 && d->tile <= 4, CN_ERR_ARG, "cn_linear: bad tile %d", d->tile);
     CN_REQUIRE(d->tile <= 2 || x6, CN_ERR_UNSUPPORTED, "cn_linear: tile %d is a bf16x6 tile", d->tile);
-    if (x6 && d->a_bf16 && CN_AB_X6_AIMG) {  // (measurement build) A as a bf16x6 term image, rows = lda
-        CN_REQUIRE(!d->A2 && !d->aux0_bf16 && !d->aux12_bf16 && !d->out0_b && !d->out1_b && d->lda >= d->M &&
-                       al16(d->A) && choose_linear_tile(d) == LT_X6_SQ,
-                   CN_ERR_UNSUPPORTED, "cn_linear: bf16x6 A images: 256x256 tile, no A2, lda = image rows >= M");
-    } else if (d->a_bf16 || d->aux0_bf16 || d->aux12_bf16 || d->out0_b || d->out1_b) {  // bf16 operand images (ABI v10)
+    if (d->a_bf16 || d->aux0_bf16 || d->aux12_bf16 || d->out0_b || d->out1_b) {  // bf16 operand images (ABI v10)
         CN_REQUIRE(bf, CN_ERR_UNSUPPORTED, "cn_linear: bf16 operand images need mfma_dtype CN_MFMA_BF16");
         CN_REQUIRE(!d->a_bf16 || (d->lda % 8 == 0 && (!d->A2 || d->lda2 % 8 == 0)), CN_ERR_ALIGN,
                    "cn_linear: bf16 A / A2 need lda, lda2 multiples of 8");

@@ -8,7 +8,9 @@
 namespace cn {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16_t;
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
@@ -53,26 +55,25 @@ __device__ __forceinline__ void bstore4(rsrc_t r, int voff, int soff, floatx4 v)
 }
 
 // The epilogues' streams (aux rows read once, outputs written once) with a cache policy of their own:
-// CN_EPI_AUX (measurement switch; 2 = nt on gfx950).
-#ifndef CN_EPI_AUX
-#define CN_EPI_AUX 2  // nt: measured faster (profiles/r6_ab.txt r6v)
-#endif
+// 2 = nt on gfx950, measured faster than the default policy (profiles/r6_ab.txt r6v).
+constexpr int kEpiPolicy = 2;
 __device__ __forceinline__ floatx4 eload4(rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, CN_EPI_AUX));
+    return __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, kEpiPolicy));
 }
 __device__ __forceinline__ float eload1(rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, CN_EPI_AUX));
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, kEpiPolicy));
 }
+// one bf16 of an aux row as its raw bits (zero-extended)
 // (bf16 aux rows keep the default policy: a 32-column block is half a 128-byte line, and nt loads do not
 // allocate it in L2 for the neighbouring block's load -- measured slower, profiles/r6_ab.txt r6v)
 __device__ __forceinline__ unsigned eload_u16(rsrc_t r, int voff, int soff) {
     return __builtin_amdgcn_raw_buffer_load_b16(r, voff, soff, 0);
 }
 __device__ __forceinline__ void estore1(rsrc_t r, int voff, int soff, float v) {
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, CN_EPI_AUX);
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, kEpiPolicy);
 }
 __device__ __forceinline__ void estore4(rsrc_t r, int voff, int soff, floatx4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, soff, CN_EPI_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, voff, soff, kEpiPolicy);
 }
 
 // bf16 operand images (ABI v10): a tile's rows of a bf16 tensor (ld in bf16 elements, a
@@ -82,27 +83,21 @@ __device__ __forceinline__ TileView tile_view_b16(const void* base, int ld, int6
     const char* b = static_cast<const char*>(base) + (row0 * ld + col0) * 2;
     return TileView{reinterpret_cast<const float*>(b), ld / 2, base ? (rows * ld - col0) * 2 : 0};
 }
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
 // one bf16 read as the fp32 value it represents
 __device__ __forceinline__ float bload_b16(rsrc_t r, int voff, int soff) {
     const unsigned short h = __builtin_amdgcn_raw_buffer_load_b16(r, voff, soff, 0);
     return __builtin_bit_cast(float, (unsigned)h << 16);
 }
-// one bf16 as its raw bits (zero-extended)
-__device__ __forceinline__ unsigned bload_u16(rsrc_t r, int voff, int soff) {
-    return __builtin_amdgcn_raw_buffer_load_b16(r, voff, soff, 0);
-}
 // four bf16 (8 bytes) as fp32 values
 __device__ __forceinline__ floatx4 bload_b16x4(rsrc_t r, int voff, int soff) {
-    const u32x2_t w = __builtin_bit_cast(u32x2_t, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
+    const u32x2 w = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
     return floatx4{__builtin_bit_cast(float, w[0] << 16), __builtin_bit_cast(float, w[0] & 0xffff0000u),
                    __builtin_bit_cast(float, w[1] << 16), __builtin_bit_cast(float, w[1] & 0xffff0000u)};
 }
 // RNE bf16 of two / four fp32 values (v_cvt_pk_bf16_f32: the rounding the GEMM staging applies)
 __device__ __forceinline__ unsigned pack_b16x2(float a, float b) {
     typedef float f2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(unsigned, __builtin_convertvector((f2){a, b}, bf16x2_t));
+    return __builtin_bit_cast(unsigned, __builtin_convertvector((f2){a, b}, bf16x2));
 }
 __device__ __forceinline__ void bstore_b16x2(rsrc_t r, int voff, int soff, float a, float b) {
     __builtin_amdgcn_raw_buffer_store_b32(pack_b16x2(a, b), r, voff, soff, 0);
@@ -110,7 +105,7 @@ __device__ __forceinline__ void bstore_b16x2(rsrc_t r, int voff, int soff, float
 __device__ __forceinline__ void bstore_b16x4(rsrc_t r, int voff, int soff, floatx4 v) {
     typedef __bf16 b4 __attribute__((ext_vector_type(4)));
     const b4 h = __builtin_convertvector(v, b4);
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, h), r, voff, soff, 0);
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, h), r, voff, soff, 0);
 }
 
 // torch.nn.Softplus(beta, threshold) on the hardware transcendentals: e = 2^(z beta
@@ -139,8 +134,6 @@ __device__ __forceinline__ float sigma_from_act(float a, float aux_c) {
 // a mask (high half), the remainders scalar v_sub_f32 (sub_f32): 20 VALU per 4 values
 // (the per-element convertvector round trip compiles to 30).
 typedef float floatx2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ floatx2 widen_bf16x2(unsigned p) {
     return floatx2{__builtin_bit_cast(float, p << 16), __builtin_bit_cast(float, p & 0xffff0000u)};
 }
@@ -148,22 +141,14 @@ __device__ __forceinline__ floatx2 widen_bf16x2(unsigned p) {
 // compiler cannot pair two of them into a v_pk_add_f32, which beside the MFMAs costs several times the
 // issue cycles of two scalar ones (MI355X_MICROARCH.md, issue-cost rows).
 __device__ __forceinline__ float sub_f32(float x, float y) {
-#if CN_SPLIT_PK
-    return x - y;
-#else
     float r;
     asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
     return r;
-#endif
 }
 __device__ __forceinline__ float add_f32(float x, float y) {
-#if CN_SPLIT_PK
-    return x + y;
-#else
     float r;
     asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
     return r;
-#endif
 }
 __device__ __forceinline__ void split3(floatx4 v, bf16x4& t0, bf16x4& t1, bf16x4& t2) {
     unsigned p0[2], p1[2], p2[2];

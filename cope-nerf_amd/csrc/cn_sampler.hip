@@ -376,16 +376,8 @@ __global__ void __launch_bounds__(256, 1) sdf_mlp_kernel(SdfMlpArgs p) {
 //    so every activation is bitwise the layer path's (cn_linear on the 128x128 tile for lin0, the
 //    256x256 tiles after, SOFTPLUS_HEAD's row-dot order for the sdf).
 // Per sample: the embedding's fp32 rows in (lin0's input, 256 B; the skip tail, 4 E B), the sdf out.
-#ifndef CN_X6Q_EXP
-#define CN_X6Q_EXP 0  // measurement builds: 1 no weight stream, 2 no softplus in the epilogue
-#endif
-#ifndef CN_X6Q_SPLIT_AHEAD
-#define CN_X6Q_SPLIT_AHEAD 1
-#endif
-#ifndef CN_X6Q_DMA
-#define CN_X6Q_DMA 1  // 0: register staging of the weight chunks (measured 6 % slower, profiles/r6_ab.txt r6h)
-#endif
-constexpr int kX6NS = CN_X6Q_DMA ? 6 : 3;  // ring slots
+// (Register staging of the weight chunks instead of the LDS-DMA ring measured 6 % slower, profiles/r6_ab.txt r6h.)
+constexpr int kX6NS = 6;            // ring slots
 constexpr int kX6Chunk = 24576;     // bytes per slot: 256 rows x 3 terms x 16 k bf16
 constexpr int kX6StepsPerBlock = 4 + 7 * 16;  // k-steps of lin0 (K = 64) and lin1 .. lin7 (K = 256)
 
@@ -457,29 +449,12 @@ __global__ void __launch_bounds__(256, 1) sdf_mlp_x6_kernel(SdfMlpX6Args p) {
                                                  0x00020000);
     };
     auto issue = [&](int g) __attribute__((always_inline)) {
-        if (CN_X6Q_EXP == 1 || !CN_X6Q_DMA) return;  // (measurement build: no weight stream)
         const rsrc_t v = chunk_view(g);
         char* dst = smem + (g % kX6NS) * kX6Chunk + wave * 6144;
 #pragma unroll
         for (int j = 0; j < 6; ++j)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(v, (__attribute__((address_space(3))) void*)(dst + j * 1024), 16,
                                                      dvo[j], 0, 0, 0);
-    };
-    // Register staging (CN_X6Q_DMA 0): a chunk's 6 pieces per lane are loaded one k-step ahead and written to their
-    // slot positions by ds_write_b128 -- about a sixth of an LDS-DMA piece's issue cycles each
-    floatx4 stg[6];
-    auto gload = [&](int g) __attribute__((always_inline)) {
-        if (CN_X6Q_EXP == 1 || CN_X6Q_DMA) return;
-        const rsrc_t v = chunk_view(g);
-#pragma unroll
-        for (int j = 0; j < 6; ++j) stg[j] = bload4(v, dvo[j], 0);
-    };
-    auto swrite = [&](int g) __attribute__((always_inline)) {
-        if (CN_X6Q_EXP == 1 || CN_X6Q_DMA) return;
-        wait_vmcnt<0>();
-        char* dst = smem + (g % kX6NS) * kX6Chunk + wave * 6144 + lane * 16;
-#pragma unroll
-        for (int j = 0; j < 6; ++j) *reinterpret_cast<floatx4*>(dst + j * 1024) = stg[j];
     };
     // weight (A operand) reads: lane l -> row (l & 31) of 32-row block ib (32 rows keep the rotation), term t,
     // k half h: logical piece 2 t + h
@@ -501,13 +476,6 @@ __global__ void __launch_bounds__(256, 1) sdf_mlp_x6_kernel(SdfMlpX6Args p) {
     int g = 0;
 #pragma unroll
     for (int d = 0; d < kX6NS - 2; ++d) issue(d);
-    if constexpr (!CN_X6Q_DMA) {  // chunks 0, 1 in their slots, chunk 2 in the staging registers
-        gload(0);
-        swrite(0);
-        gload(1);
-        swrite(1);
-        gload(2);
-    }
 
     floatx4 act[16][2];  // the current layer's input: k-step ks, lane half h: features 16 ks + 8 h + 4 e + (0..3)
     floatx16 acc[8];
@@ -524,8 +492,6 @@ __global__ void __launch_bounds__(256, 1) sdf_mlp_x6_kernel(SdfMlpX6Args p) {
                                 act[ks][e];
         }
     };
-    // one 16-deep k-step (stream position g) of the layer: the activations' terms, then per output block
-    // the six products in the layer path's order
     // weight terms 0 and 1 of the current k-step's eight blocks: read at the end of the previous k-step (its
     // last products then run beside those reads), term 2 mid-step
     bf16x8 w0[8], w1[8];
@@ -542,22 +508,13 @@ __global__ void __launch_bounds__(256, 1) sdf_mlp_x6_kernel(SdfMlpX6Args p) {
     // k-step g's chunk certified landed by every wave (this wave's pieces: the NS - 3 later chunks may fly;
     // the barrier: every wave's, and every wave done reading chunk g - 2's slot, which the DMA issued here
     // refills with chunk g + NS - 2)
-    // (register staging: the barrier certifies chunk g written by every wave a step earlier -- each wave's
-    // writes retired by the lgkmcnt(0) -- and every wave done with chunk g - 2's slot)
     auto land = [&](int gg) __attribute__((always_inline)) {
-        if constexpr (CN_X6Q_DMA) {
-            wait_vmcnt<6 * (kX6NS - 3)>();
-        } else {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        }
+        wait_vmcnt<6 * (kX6NS - 3)>();
         asm volatile("" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         issue(gg + kX6NS - 2);
     };
-    // one 16-deep k-step (stream position g) of the layer: the activations' terms, then per output block the
-    // six products in the layer path's order; chunk g + 1 is certified and its terms 0, 1 read before the
-    // sixth product
     // the three terms of k-step ks's activations (the layer path splits them while staging: the same split3)
     auto split_act = [&](int ks, bf16x8& b0, bf16x8& b1, bf16x8& b2) __attribute__((always_inline)) {
         bf16x4 a0[2], a1[2], a2[2];
@@ -567,12 +524,15 @@ __global__ void __launch_bounds__(256, 1) sdf_mlp_x6_kernel(SdfMlpX6Args p) {
         b1 = __builtin_shufflevector(a1[0], a1[1], 0, 1, 2, 3, 4, 5, 6, 7);
         b2 = __builtin_shufflevector(a2[0], a2[1], 0, 1, 2, 3, 4, 5, 6, 7);
     };
-    bf16x8 nb0, nb1, nb2;  // (CN_X6Q_SPLIT_AHEAD) the next k-step's terms, split beside this step's products
+    bf16x8 nb0, nb1, nb2;  // the next k-step's terms, split beside this step's products
+    // one 16-deep k-step (stream position g) of the layer: the activations' terms, then per output block the
+    // six products in the layer path's order; chunk g + 1 is certified and its terms 0, 1 read before the
+    // sixth product
     auto kstep_n = [&](auto ks_c, auto nks_c) __attribute__((always_inline)) {
         constexpr int ks = decltype(ks_c)::value, NKS = decltype(nks_c)::value;
         const uint32_t sb = lds0 + (g % kX6NS) * kX6Chunk + aoff[2];
         bf16x8 b0, b1, b2;
-        if (CN_X6Q_SPLIT_AHEAD && ks > 0) {
+        if (ks > 0) {
             b0 = nb0;
             b1 = nb1;
             b2 = nb2;
@@ -586,7 +546,7 @@ __global__ void __launch_bounds__(256, 1) sdf_mlp_x6_kernel(SdfMlpX6Args p) {
         for (int ib = 0; ib < 8; ++ib) acc[ib] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0[ib], b0, acc[ib], 0, 0, 0);
 #pragma unroll
         for (int ib = 0; ib < 8; ++ib) acc[ib] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0[ib], b1, acc[ib], 0, 0, 0);
-        if constexpr (CN_X6Q_SPLIT_AHEAD && ks + 1 < NKS) split_act(ks + 1, nb0, nb1, nb2);
+        if constexpr (ks + 1 < NKS) split_act(ks + 1, nb0, nb1, nb2);
         bf16x8 w2[8];
         static_for<8>([&](auto ib_c) {
             constexpr int ib = decltype(ib_c)::value;
@@ -602,8 +562,6 @@ __global__ void __launch_bounds__(256, 1) sdf_mlp_x6_kernel(SdfMlpX6Args p) {
 #pragma unroll
         for (int ib = 0; ib < 8; ++ib) acc[ib] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1[ib], b1, acc[ib], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
-        swrite(g + 2);  // (register staging) chunk g + 2, loaded a step ago, into chunk g - 1's slot
-        gload(g + 3);
         land(g + 1);
         read_w(g + 1, std::integral_constant<int, 0>{});
         asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(w2[0]), "+v"(w2[1]), "+v"(w2[2]), "+v"(w2[3]), "+v"(w2[4]),
@@ -637,8 +595,7 @@ __global__ void __launch_bounds__(256, 1) sdf_mlp_x6_kernel(SdfMlpX6Args p) {
         constexpr int ib = decltype(ib_c)::value;
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-            o[r] = CN_X6Q_EXP == 2 ? acc[ib][r] + bb[r >> 2][r & 3]  // (measurement build: no softplus)
-                                   : softplus_hw(acc[ib][r] + bb[r >> 2][r & 3], c_exp, c_thr, c_log);
+            o[r] = softplus_hw(acc[ib][r] + bb[r >> 2][r & 3], c_exp, c_thr, c_log);
         if (l == p.skip_layer) {
             const float inv_odiv = p.inv_odiv[l];
 #pragma unroll

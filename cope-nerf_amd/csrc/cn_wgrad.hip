@@ -501,15 +501,6 @@ __global__ void __launch_bounds__(128 * WM, 2) wgrad_x6_kernel(WgradArgs p) {
 // 767-772 vs 790-794 us per 2-pair C2-shape call on random data, 641-644 vs 666-676 with
 // L2-resident operands (the kernel is not HBM-bound); 16x16x32 MFMAs (higher clock, more
 // cycles) and a register-held split of the next 32-row chunk measured equal to the old kernel.
-#ifndef CN_WGRAD_DMA_NT
-#define CN_WGRAD_DMA_NT 1  // wgrad_b16d_kernel's image rows loaded non-temporally (profiles/r6_ab.txt r6x)
-#endif
-#ifndef CN_WGRAD_NT
-#define CN_WGRAD_NT 1  // wgrad_x6r_kernel's raw rows loaded non-temporally (profiles/r6_ab.txt r6w)
-#endif
-#ifndef CN_WGRAD_TIED_LOADS
-#define CN_WGRAD_TIED_LOADS 0  // 1: measured slower (profiles/r6_ab.txt r6i)
-#endif
 template <int NRAW>
 __global__ void __launch_bounds__(512, 2) wgrad_x6r_kernel(WgradBatch batch) {
     constexpr int BNo = 256, MC = 16, PL = 8, LSB = 3 * PL + 4;  // 28 dwords per LDS row
@@ -555,25 +546,9 @@ __global__ void __launch_bounds__(512, 2) wgrad_x6r_kernel(WgradBatch batch) {
         const int nrows = valid ? min(MC, mend - mrow) : 0;
         const int col0 = sx ? k0 : n0;
         const rsrc_t v = make_view(src + (int64_t)mrow * ld + col0, (nrows * ld - col0) * 4);
+        // (the raw rows are read once: non-temporally, profiles/r6_ab.txt r6w)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-#if CN_WGRAD_TIED_LOADS
-            // the load writes the set's own registers ("+v": the old value's), so the two register sets keep
-            // their places across the loop's back edge -- compiled loads got fresh destinations there, and the
-            // copies back (16 v_mov per two stages) waited for the loads one stage early (vmcnt(0) at the
-            // back edge).  The asm loads are not counted by the compiler: wait_set() waits for them.
-            const int off = ((mq * 4 + r) * ld + cg * 4) * 4;
-            asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "+v"(r4[r]) : "v"(off), "s"(v));
-#else
-            r4[r] = CN_WGRAD_NT ? eload4(v, ((mq * 4 + r) * ld + cg * 4) * 4, 0) : bload4(v, ((mq * 4 + r) * ld + cg * 4) * 4, 0);
-#endif
-        }
-    };
-    // (CN_WGRAD_TIED_LOADS) a set loaded a stage ago has landed: only the 4 loads issued since may fly
-    auto wait_set = [&](floatx4 (&r4)[4]) {
-#if CN_WGRAD_TIED_LOADS
-        asm volatile("s_waitcnt vmcnt(4)" : "+v"(r4[0]), "+v"(r4[1]), "+v"(r4[2]), "+v"(r4[3]));
-#endif
+        for (int r = 0; r < 4; ++r) r4[r] = eload4(v, ((mq * 4 + r) * ld + cg * 4) * 4, 0);
     };
     // split column e of the 4 x 4 block of a register set into the stage image of buffer `buf`
     // (WB: the bias sums are taken at all -- only the Y waves of a job's first output tile; the other waves'
@@ -643,10 +618,8 @@ __global__ void __launch_bounds__(512, 2) wgrad_x6r_kernel(WgradBatch batch) {
     // the loop body stays one basic block
     const bool ybias = do_bias & !sx;
     auto bias_of = [&](int c) { return ybias & (c < nch); };
-    static_assert(!CN_WGRAD_TIED_LOADS || NRAW == 2, "wait_set counts one other set of 4 loads");
 #pragma unroll
     for (int s = 0; s < NRAW; ++s) gload(s, raw[s]);
-    wait_set(raw[0]);
     splitw(raw[0], 0, bias_of(0));
     __syncthreads();
     // stage c in set c % NRAW: the loop is unrolled NRAW-fold so the set indices are constants,
@@ -658,7 +631,6 @@ __global__ void __launch_bounds__(512, 2) wgrad_x6r_kernel(WgradBatch batch) {
                 const int c = c0 + k;
                 {
                     gload(c + NRAW, raw[k]);  // set k held stage c (split in the previous stage)
-                    wait_set(raw[(k + 1) % NRAW]);
                     const bool bnext = bias_of(c + 1);
                     compute(c & 1, [&](int j) { split_col(wb_tag, raw[(k + 1) % NRAW], j, (c + 1) & 1, bnext); });
                     __syncthreads();  // stage c+1 written, stage c's buffer free
@@ -776,10 +748,10 @@ __global__ void __launch_bounds__(512, 2) wgrad_b16r_kernel(WgradBatch batch) {
                 const float f0 = r8[0][d], f1 = r8[1][d], f2 = r8[2][d], f3 = r8[3][d];
                 const unsigned w0 = __builtin_bit_cast(unsigned, f0), w1 = __builtin_bit_cast(unsigned, f1);
                 const unsigned w2 = __builtin_bit_cast(unsigned, f2), w3 = __builtin_bit_cast(unsigned, f3);
-                const u32x2_t lo = {__builtin_amdgcn_perm(w1, w0, 0x05040100u), __builtin_amdgcn_perm(w3, w2, 0x05040100u)};
-                const u32x2_t hi = {__builtin_amdgcn_perm(w1, w0, 0x07060302u), __builtin_amdgcn_perm(w3, w2, 0x07060302u)};
-                *reinterpret_cast<u32x2_t*>(img + (cg * 8 + 2 * d) * LSB) = lo;
-                *reinterpret_cast<u32x2_t*>(img + (cg * 8 + 2 * d + 1) * LSB) = hi;
+                const u32x2 lo = {__builtin_amdgcn_perm(w1, w0, 0x05040100u), __builtin_amdgcn_perm(w3, w2, 0x05040100u)};
+                const u32x2 hi = {__builtin_amdgcn_perm(w1, w0, 0x07060302u), __builtin_amdgcn_perm(w3, w2, 0x07060302u)};
+                *reinterpret_cast<u32x2*>(img + (cg * 8 + 2 * d) * LSB) = lo;
+                *reinterpret_cast<u32x2*>(img + (cg * 8 + 2 * d + 1) * LSB) = hi;
                 if (bias) {
                     bsum[2 * d] += (__builtin_bit_cast(float, w0 << 16) + __builtin_bit_cast(float, w1 << 16)) +
                                    (__builtin_bit_cast(float, w2 << 16) + __builtin_bit_cast(float, w3 << 16));
@@ -965,12 +937,12 @@ __global__ void __launch_bounds__(512, 2) wgrad_b16d_kernel(WgradBatch batch) {
         const int64_t base = (pair ? src1 : src0) + (int64_t)r0 * ld * 2;
         const rsrc_t v = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(base), 0, bytes, 0x00020000);
         char* dst = smem + (c % NS) * STAGE + (sx ? SIDE : 0) + wq * 8 * ROWB;
+        // (cache policy 2: the image rows are read once, non-temporally, profiles/r6_ab.txt r6x)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int row = wq * 8 + 2 * j + drow;
             const int ch = dch ^ ((row & 3) << 2);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(v, (lds_void*)(dst + j * 1024), 16, row * ld * 2 + ch * 16,
-                                                     0, 0, CN_WGRAD_DMA_NT ? 2 : 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(v, (lds_void*)(dst + j * 1024), 16, row * ld * 2 + ch * 16, 0, 0, 2);
         }
     };
 
