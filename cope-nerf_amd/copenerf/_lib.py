@@ -166,6 +166,22 @@ class MeshDesc(ctypes.Structure):
     ]
 
 
+class PointColorsDesc(ctypes.Structure):
+    _fields_ = [
+        ("M", c_i64), ("x", c_ptr), ("time_step", c_ptr), ("sdf_net", ctypes.POINTER(SdfNet)),
+        ("color_net", ctypes.POINTER(ColorNet)), ("view_dir", ctypes.POINTER(c_f32)), ("chunk_rows", c_i32),
+        ("rgb", c_ptr), ("rgb8", c_ptr), ("grad", c_ptr),
+    ]
+
+
+class MeshCleanDesc(ctypes.Structure):
+    _fields_ = [
+        ("V", c_i32), ("T", c_i32), ("triangles", c_ptr), ("label", c_ptr), ("tri_count", c_ptr),
+        ("keep_largest", c_i32), ("min_triangles", c_i32), ("counts", c_ptr), ("kept_vertices", c_ptr),
+        ("max_vertices", c_i64), ("triangles_out", c_ptr), ("max_triangles", c_i64),
+    ]
+
+
 LPIPS_CONVS, LPIPS_TAPS = 13, 5
 
 
@@ -259,6 +275,16 @@ SIGNATURES = {
     "cn_mesh_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32]),
     "cn_mesh_count": (c_i32, [ctypes.POINTER(MeshDesc), c_ptr, c_i64, c_ptr]),
     "cn_mesh_emit": (c_i32, [ctypes.POINTER(MeshDesc), c_ptr, c_i64, c_ptr]),
+    "cn_vertex_dirs": (c_i32, [c_i64, c_ptr, c_i64, c_f32, c_ptr, c_ptr]),
+    "cn_rgb8_pack": (c_i32, [c_i64, c_ptr, c_ptr, c_ptr]),
+    "cn_point_colors_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(PointColorsDesc)]),
+    "cn_point_colors": (c_i32, [ctypes.POINTER(PointColorsDesc), c_ptr, c_i64, c_ptr]),
+    "cn_mesh_label_init": (c_i32, [ctypes.POINTER(MeshCleanDesc), c_ptr]),
+    "cn_mesh_label_rounds": (c_i32, [ctypes.POINTER(MeshCleanDesc), c_i32, c_ptr, c_ptr]),
+    "cn_mesh_component_sizes": (c_i32, [ctypes.POINTER(MeshCleanDesc), c_ptr]),
+    "cn_mesh_clean_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32]),
+    "cn_mesh_select": (c_i32, [ctypes.POINTER(MeshCleanDesc), c_ptr, c_i64, c_ptr]),
+    "cn_mesh_compact": (c_i32, [ctypes.POINTER(MeshCleanDesc), c_ptr, c_i64, c_ptr]),
     "cn_refine_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32]),
     "cn_refine_warp": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
                                c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),

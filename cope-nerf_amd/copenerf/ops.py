@@ -1123,6 +1123,180 @@ def isosurface(u, threshold, lo, hi):
 
 
 # ---------------------------------------------------------------------------
+# Vertex colours and floater removal (additive to ABI v22)
+def vertex_dirs(G, sign=-1.0, out=None):
+    """dirs [M, 3] = sign * G[:, :3] / max(|G[:, :3]|, 1e-12) -- cn_vertex_dirs (G: rows of ∇ₓSDF, [M, >= 3]);
+    sign -1: the inward unit normals, the view directions of vertex colours."""
+    _need(G, "G")
+    if G.dtype != torch.float32 or G.shape[1] < 3:
+        raise RuntimeError(f"vertex_dirs: G must be fp32 [M, >= 3] (got {G.dtype} {tuple(G.shape)})")
+    M = G.shape[0]
+    if out is None:
+        out = torch.empty(M, 3, device=G.device)
+    _need(out, "out")
+    if out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (M, 3):
+        raise RuntimeError("vertex_dirs: out must be a contiguous fp32 [M, 3] tensor")
+    _lib.call("cn_vertex_dirs", M, _ptr(G), _ld(G) if M else 4, float(sign), _ptr(out), _stream())
+    return out
+
+
+def rgb8_pack(rgb, out=None):
+    """uint8 floor(clamp(rgb, 0, 1) * 255 + 0.5) of a contiguous fp32 tensor, NaN -> 0 -- cn_rgb8_pack."""
+    _need(rgb, "rgb", ndim=0)
+    if rgb.dtype != torch.float32 or not rgb.is_contiguous():
+        raise RuntimeError("rgb8_pack: rgb must be a contiguous fp32 tensor")
+    if out is None:
+        out = torch.empty(rgb.shape, dtype=torch.uint8, device=rgb.device)
+    if out.dtype != torch.uint8 or not out.is_contiguous() or out.shape != rgb.shape or out.device != rgb.device:
+        raise RuntimeError("rgb8_pack: out must be a contiguous uint8 tensor of rgb's shape on its device")
+    _lib.call("cn_rgb8_pack", rgb.numel(), _ptr(rgb), _ptr(out), _stream())
+    return out
+
+
+def point_colors(sdf_net_, color_net_, x, t, view_dir=None, chunk_rows=0, want_rgb8=False, want_grad=False):
+    """The colour network at the device points x [M, 3] and the time value t (a 1-element device tensor), the
+    view direction the inward unit normal of every point or, with view_dir (three host floats), that one
+    direction normalised -- cn_point_colors with the networks' descriptors (sdf_net, color_net with the folded
+    first layer).  Returns rgb fp32 [M, 3], then rgb8 uint8 [M, 3] and / or grad fp32 [M, 4] where asked."""
+    _need(x, "x")
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.shape[1] != 3:
+        raise RuntimeError(f"point_colors: x must be a contiguous fp32 [M, 3] tensor (got {x.dtype} {tuple(x.shape)})")
+    M, dev = x.shape[0], x.device
+    t = device_scalar(t, dev)
+    rgb = torch.empty(M, 3, device=dev)
+    rgb8 = torch.empty(M, 3, dtype=torch.uint8, device=dev) if want_rgb8 else None
+    grad = torch.empty(M, 4, device=dev) if want_grad else None
+    d = _lib.PointColorsDesc()
+    d.M, d.x, d.time_step, d.chunk_rows = M, _ptr(x), _ptr(t), int(chunk_rows)
+    d.sdf_net, d.color_net = ctypes.pointer(sdf_net_), ctypes.pointer(color_net_)
+    if view_dir is not None:
+        v = [float(c) for c in (view_dir.tolist() if hasattr(view_dir, "tolist") else view_dir)]
+        if len(v) != 3:
+            raise RuntimeError("point_colors: view_dir must have three entries")
+        vd = (_lib.c_f32 * 3)(*v)
+        d.view_dir = ctypes.cast(vd, ctypes.POINTER(_lib.c_f32))
+    d.rgb, d.rgb8, d.grad = _ptr(rgb), _ptr(rgb8), _ptr(grad)
+    lib = _lib.load()
+    ws = torch.empty(max(int(lib.cn_point_colors_workspace_bytes(ctypes.byref(d))), 1), dtype=torch.uint8, device=dev)
+    _lib.check(lib.cn_point_colors(ctypes.byref(d), _ptr(ws), ws.numel(), _stream()), "cn_point_colors")
+    out = (rgb,) + ((rgb8,) if want_rgb8 else ()) + ((grad,) if want_grad else ())
+    return out[0] if len(out) == 1 else out
+
+
+# rounds between two reads of the device's `changed` flag: the first call's, doubled call by call up to the cap
+LABEL_ROUNDS_PER_CALL, LABEL_ROUNDS_PER_CALL_MAX = 8, 256
+
+
+def _mesh_clean_desc(fn, triangles, V):
+    _need(triangles, "triangles")
+    if triangles.dtype != torch.int32 or not triangles.is_contiguous() or triangles.shape[1] != 3:
+        raise RuntimeError(f"{fn}: triangles must be a contiguous int32 [T, 3] device tensor")
+    d = _lib.MeshCleanDesc()
+    d.V, d.T = int(V), triangles.shape[0]
+    d.triangles = _ptr(triangles) if d.T else None
+    return d
+
+
+def mesh_components_cap(V):
+    """The most rounds mesh_components launches for V vertices."""
+    return int(V) + 2 * LABEL_ROUNDS_PER_CALL_MAX
+
+
+def mesh_components(triangles, V, rounds_per_call=LABEL_ROUNDS_PER_CALL):
+    """(label int32 [V], rounds): label[v] = the smallest vertex id of v's connected component in the indexed
+    triangle list triangles int32 [T, 3] over V vertices -- cn_mesh_label_init, then cn_mesh_label_rounds in
+    calls of rounds_per_call rounds, doubled call by call up to LABEL_ROUNDS_PER_CALL_MAX, until the device's
+    `changed` flag reads clear (one 4-byte read-back per call, like isosurface's read of the counts).  rounds
+    counts every round launched, the confirming ones included.  The cap is V + 2 LABEL_ROUNDS_PER_CALL_MAX
+    rounds: round r settles every vertex within r edges of its component's smallest id, so V rounds always
+    suffice; labels still changing at the cap raise a RuntimeError."""
+    d = _mesh_clean_desc("mesh_components", triangles, V)
+    dev = triangles.device
+    label = torch.empty(d.V, dtype=torch.int32, device=dev)
+    d.label = _ptr(label) if d.V else None
+    _lib.call("cn_mesh_label_init", ctypes.byref(d), _stream())
+    rounds, cap, k = 0, mesh_components_cap(d.V), max(int(rounds_per_call), 1)
+    if d.V == 0 or d.T == 0:
+        return label, rounds
+    changed = torch.empty(1, dtype=torch.int32, device=dev)
+    while True:
+        _lib.call("cn_mesh_label_rounds", ctypes.byref(d), k, _ptr(changed), _stream())
+        rounds += k
+        if not int(changed.item()):
+            return label, rounds
+        if rounds >= cap:
+            raise RuntimeError(f"mesh_components: labels still changing after {rounds} rounds (cap {cap})")
+        k = min(2 * k, LABEL_ROUNDS_PER_CALL_MAX, cap - rounds)
+
+
+def mesh_component_sizes(triangles, label):
+    """tri_count int32 [V]: the triangles of every component at its root id, 0 elsewhere --
+    cn_mesh_component_sizes (label: mesh_components')."""
+    d = _mesh_clean_desc("mesh_component_sizes", triangles, label.shape[0])
+    if label.dtype != torch.int32 or not label.is_contiguous() or label.device != triangles.device:
+        raise RuntimeError("mesh_component_sizes: label must be a contiguous int32 [V] tensor on triangles' device")
+    tri_count = torch.empty_like(label)
+    d.label, d.tri_count = (_ptr(label), _ptr(tri_count)) if d.V else (None, None)
+    _lib.call("cn_mesh_component_sizes", ctypes.byref(d), _stream())
+    return tri_count
+
+
+def mesh_select(triangles, label, tri_count, keep_largest=False, min_triangles=0):
+    """The select pass of mesh_clean -- cn_mesh_select: (descriptor, workspace, counts) with counts a device
+    int64 [2] = (kept vertices, kept triangles); the workspace keeps the flags and offsets mesh_compact reads."""
+    d = _mesh_clean_desc("mesh_select", triangles, label.shape[0])
+    dev = triangles.device
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    d.label, d.tri_count = (_ptr(label), _ptr(tri_count)) if d.V else (None, None)
+    d.keep_largest, d.min_triangles, d.counts = int(bool(keep_largest)), int(min_triangles), _ptr(counts)
+    lib = _lib.load()
+    ws = torch.empty(max(int(lib.cn_mesh_clean_workspace_bytes(d.V, d.T)), 1), dtype=torch.uint8, device=dev)
+    _lib.check(lib.cn_mesh_select(ctypes.byref(d), _ptr(ws), ws.numel(), _stream()), "cn_mesh_select")
+    return d, ws, counts
+
+
+def mesh_compact(d, ws, kept_vertices, triangles_out, counts=None):
+    """The compact pass -- cn_mesh_compact into kept_vertices int32 [V'] / triangles_out int32 [T', 3] with
+    mesh_select's descriptor and workspace.  counts: the (V', T') read back from mesh_select, checked here against
+    the buffers (the kernel checks the device counts again and writes nothing into buffers that are too small)."""
+    for t, nm in ((kept_vertices, "kept_vertices"), (triangles_out, "triangles_out")):
+        if t.dtype != torch.int32 or not t.is_contiguous() or not t.is_cuda:
+            raise RuntimeError(f"mesh_compact: {nm} must be a contiguous int32 device tensor")
+    if kept_vertices.dim() != 1 or triangles_out.dim() != 2 or triangles_out.shape[1] != 3:
+        raise RuntimeError("mesh_compact: kept_vertices [V'] and triangles_out [T', 3]")
+    if counts is not None and (kept_vertices.shape[0] < counts[0] or triangles_out.shape[0] < counts[1]):
+        raise RuntimeError(f"mesh_compact: buffers of {kept_vertices.shape[0]} vertices / {triangles_out.shape[0]} "
+                           f"triangles for counts {tuple(counts)}")
+    d.kept_vertices, d.max_vertices = _ptr(kept_vertices) if kept_vertices.shape[0] else None, kept_vertices.shape[0]
+    d.triangles_out, d.max_triangles = _ptr(triangles_out) if triangles_out.shape[0] else None, triangles_out.shape[0]
+    _lib.call("cn_mesh_compact", ctypes.byref(d), _ptr(ws), ws.numel(), _stream())
+
+
+def mesh_clean(vertices, triangles, keep_largest=False, min_triangles=0, stats=None):
+    """Floater removal on the device: the mesh without the connected components that are not kept.  A component
+    is kept if it has at least min_triangles triangles and, with keep_largest, is the one with the most triangles
+    (a tie goes to the smaller smallest-vertex id).  Returns (vertices' [V', 3], triangles' int32 [T', 3]
+    renumbered, kept_vertices int32 [V']: the original ids, ascending); kept vertices and triangles keep their
+    order.  Labels (mesh_components), sizes, select, one 16-byte read-back, an exact allocation, compact,
+    index_select.  stats: an optional dict that receives components / components_kept / rounds."""
+    _need(vertices, "vertices")
+    V = vertices.shape[0]
+    label, rounds = mesh_components(triangles, V)
+    tri_count = mesh_component_sizes(triangles, label)
+    d, ws, counts = mesh_select(triangles, label, tri_count, keep_largest, min_triangles)
+    Vk, Tk = (int(c) for c in counts.tolist())
+    kept = torch.empty(Vk, dtype=torch.int32, device=triangles.device)
+    tri = torch.empty(Tk, 3, dtype=torch.int32, device=triangles.device)
+    mesh_compact(d, ws, kept, tri, (Vk, Tk))
+    if stats is not None:
+        roots = label == torch.arange(V, dtype=torch.int32, device=label.device)
+        stats["components"] = int(roots.sum())
+        stats["components_kept"] = int(roots[kept.long()].sum()) if Vk else 0
+        stats["rounds"] = rounds
+    return vertices.index_select(0, kept.long()), tri, kept
+
+
+# ---------------------------------------------------------------------------
 # Pose refinement (ABI v17)
 class _RefineWarp(torch.autograd.Function):
     """cn_refine_warp: the forward launches the fused pass and keeps dpose = d sums[:, 0] / d pose; the

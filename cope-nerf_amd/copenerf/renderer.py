@@ -428,27 +428,82 @@ class NeuSRenderer(nn.Module):
         del keep
         return u
 
+    def _fixed_dir(self, view_dir, dev):
+        """view_dir as cn_point_colors normalises it: (float)(v / |v|), the quotient in double."""
+        v = torch.as_tensor(view_dir, dtype=torch.float32).reshape(-1).double()
+        if v.numel() != 3 or not bool(v.norm() > 0):
+            raise ValueError("vertex_colors: view_dir must be three numbers, not all zero")
+        return (v / torch.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])).float().to(dev)
+
     @torch.no_grad()
-    def extract_geometry(self, bound_min, bound_max, resolution, threshold=0.0, time_step=0.0, with_normals=False):
+    def vertex_colors(self, vertices, time_step=0.0, view_dir=None, chunk_rows=0):
+        """rgb float32 [V, 3] (device): the colour network at the device points vertices [V, 3] and the time value
+        time_step, the view direction of every point its inward unit normal -n̂ (n̂ the normalised first three
+        columns of ∇ₓSDF: the usual convention for vertex colours) or, with view_dir (three numbers), that one
+        direction, normalised, on every point.  One cn_point_colors call where the feature head folds; otherwise
+        the module composition in chunks of chunk_rows rows (0: 2^18), the route forward takes when it cannot
+        fold: SDFNetwork.field, ops.vertex_dirs, RenderingNetwork.color."""
+        dev = next(self.sdf_network.parameters()).device
+        if dev.type != "cuda" or not vertices.is_cuda:
+            raise RuntimeError(f"copenerf: vertex_colors needs the module and the vertices on a CUDA/HIP device "
+                               f"(got {dev}, {vertices.device}); the HIP kernels have no CPU fallback")
+        vertices = vertices.detach().float().contiguous()
+        t = ops.device_scalar(time_step, dev)
+        sdf_packed = self.sdf_network.params_and_pack()
+        fold = self._can_fold()
+        col_packed = self.color_network.params_and_pack(
+            fold_feature=(sdf_packed[0][-1], sdf_packed[1][-1]) if fold else None)
+        if fold:
+            sn, k1 = ops.sdf_net(self.sdf_network.layout(), sdf_packed[2])
+            cn, k2 = ops.color_net(self.color_network.layout(), col_packed[2])
+            rgb = ops.point_colors(sn, cn, vertices, t, view_dir=view_dir, chunk_rows=chunk_rows)
+            del k1, k2
+            return rgb
+        fixed = None if view_dir is None else self._fixed_dir(view_dir, dev)
+        V = vertices.shape[0]
+        rgb = torch.empty(V, 3, device=dev)
+        chunk = int(chunk_rows) if chunk_rows else 1 << 18
+        for i in range(0, V, chunk):
+            v = vertices[i:i + chunk]
+            pts_time = torch.cat([v, t.expand(v.shape[0], 1)], dim=1)
+            _, feat, G = self.sdf_network.field(pts_time, want_feat=True, want_grad=True, packed=sdf_packed)
+            dirs = ops.vertex_dirs(G) if fixed is None else fixed.expand(v.shape[0], 3).contiguous()
+            rgb[i:i + chunk] = self.color_network.color(pts_time, G, dirs, 1, feat, packed=col_packed)
+        return rgb
+
+    @torch.no_grad()
+    def extract_geometry(self, bound_min, bound_max, resolution, threshold=0.0, time_step=0.0, with_normals=False,
+                         with_colors=False, view_dir=None, keep_largest=False, min_triangles=0, stats=None):
         """The surface sdf(x, y, z, time_step) = threshold inside the box as a welded triangle mesh (reference:
         neus_renderer.py:28-36, 588-591; the first four arguments are the reference's): numpy vertices float32
         [V, 3] and triangles int32 [T, 3], with with_normals also unit normals float32 [V, 3] (the normalised
-        SDFNetwork.gradient at (vertex, time_step)).
+        SDFNetwork.gradient at (vertex, time_step)), with with_colors after them uint8 colours [V, 3]
+        (vertex_colors at (vertex, time_step), view_dir as there, packed by ops.rgb8_pack).
+
+        keep_largest / min_triangles remove floaters first (ops.mesh_clean: only the connected component with the
+        most triangles / only those with at least min_triangles), so normals and colours are computed for kept
+        vertices only; with both off the mesh is untouched.  stats: an optional dict that receives the number of
+        components found and kept when the mesh is cleaned.
 
         The volume holds +sdf (the reference meshes -sdf with PyMCubes): triangles are oriented so that their
         normals point toward larger sdf, out of the surface.  Marching tetrahedra on the Kuhn split
-        (ops.isosurface); the volume never leaves the device."""
+        (ops.isosurface); neither the volume nor the mesh leaves the device before the final copy."""
         dev = next(self.sdf_network.parameters()).device
         u = self.sdf_volume(bound_min, bound_max, resolution, time_step)
         vertices, triangles = ops.isosurface(u, threshold, bound_min, bound_max)
+        if keep_largest or min_triangles:
+            vertices, triangles, _ = ops.mesh_clean(vertices, triangles, keep_largest, min_triangles, stats=stats)
         out = (vertices.cpu().numpy(), triangles.cpu().numpy())
-        if not with_normals:
-            return out
-        t = ops.device_scalar(time_step, dev)
-        normals = torch.empty_like(vertices)
-        chunk = 1 << 18
-        for i in range(0, vertices.shape[0], chunk):
-            v = vertices[i:i + chunk]
-            g = self.sdf_network.gradient(torch.cat([v, t.expand(v.shape[0], 1)], dim=1))[:, 0, :3]
-            normals[i:i + chunk] = torch.nn.functional.normalize(g, dim=-1)
-        return out + (normals.cpu().numpy(),)
+        if with_normals:
+            t = ops.device_scalar(time_step, dev)
+            normals = torch.empty_like(vertices)
+            chunk = 1 << 18
+            for i in range(0, vertices.shape[0], chunk):
+                v = vertices[i:i + chunk]
+                g = self.sdf_network.gradient(torch.cat([v, t.expand(v.shape[0], 1)], dim=1))[:, 0, :3]
+                normals[i:i + chunk] = torch.nn.functional.normalize(g, dim=-1)
+            out += (normals.cpu().numpy(),)
+        if with_colors:
+            rgb = self.vertex_colors(vertices, time_step, view_dir=view_dir)
+            out += (ops.rgb8_pack(rgb).cpu().numpy(),)
+        return out

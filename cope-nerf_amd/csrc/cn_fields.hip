@@ -190,6 +190,31 @@ __global__ void __launch_bounds__(256) color_extras_bwd_kernel(int R, int rows, 
     }
 }
 
+// dirs[m] = sign * G[m][0:3] / max(|G[m][0:3]|, 1e-12): one thread per row (a grid-stride loop past 2^24
+// rows).  The norm is the plain sum of squares, left to right, never contracted to FMAs, so a host
+// restatement rounds the same way; a zero row divides 0 by 1e-12: exact zeros.
+__global__ void __launch_bounds__(256) vertex_dirs_kernel(int64_t M, const float* __restrict__ G, int64_t ldg,
+                                                          float sign, float* __restrict__ dirs) {
+#pragma clang fp contract(off)
+    for (int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x; m < M; m += (int64_t)gridDim.x * 256) {
+        const float gx = G[m * ldg], gy = G[m * ldg + 1], gz = G[m * ldg + 2];
+        const float n = fmaxf(sqrtf((gx * gx + gy * gy) + gz * gz), 1e-12f);
+        dirs[3 * m] = sign * gx / n;
+        dirs[3 * m + 1] = sign * gy / n;
+        dirs[3 * m + 2] = sign * gz / n;
+    }
+}
+
+// 8-bit colours: floor(clamp(v, 0, 1) * 255 + 0.5); fmaxf(NaN, 0) = 0, so NaN -> 0
+__global__ void __launch_bounds__(256) rgb8_pack_kernel(int64_t n, const float* __restrict__ rgb,
+                                                        uint8_t* __restrict__ out) {
+#pragma clang fp contract(off)
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+        out[i] = (uint8_t)floorf(fminf(fmaxf(rgb[i], 0.0f), 1.0f) * 255.0f + 0.5f);
+}
+
+static int stride_blocks(int64_t n) { return (int)((n + 255) / 256 < 65536 ? (n + 255) / 256 : 65536); }
+
 static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace cn
@@ -277,4 +302,22 @@ extern "C" int cn_color_extras_bwd(int32_t R, int32_t dir_div, const float* d_ex
     color_extras_bwd_kernel<<<cdiv(R, 8), 256, 0, (hipStream_t)stream>>>(R, dir_div, d_ext, ld_ext, dirs, ld_d,
                                                                         multires_view, ddirs, accumulate);
     return check_launch("cn_color_extras_bwd");
+}
+
+extern "C" int cn_vertex_dirs(int64_t M, const float* G, int64_t ldg, float sign, float* dirs, cn_stream_t stream) {
+    CN_REQUIRE(M >= 0 && ldg >= 3, CN_ERR_SHAPE, "cn_vertex_dirs: M=%lld ldg=%lld", (long long)M, (long long)ldg);
+    if (M == 0) return CN_OK;
+    CN_REQUIRE(G && dirs, CN_ERR_ARG, "cn_vertex_dirs: null pointer");
+    CN_REQUIRE(((uintptr_t)G & 3) == 0 && ((uintptr_t)dirs & 3) == 0, CN_ERR_ALIGN, "cn_vertex_dirs: alignment");
+    vertex_dirs_kernel<<<stride_blocks(M), 256, 0, (hipStream_t)stream>>>(M, G, ldg, sign, dirs);
+    return check_launch("cn_vertex_dirs");
+}
+
+extern "C" int cn_rgb8_pack(int64_t n, const float* rgb, uint8_t* out, cn_stream_t stream) {
+    CN_REQUIRE(n >= 0, CN_ERR_SHAPE, "cn_rgb8_pack: n=%lld", (long long)n);
+    if (n == 0) return CN_OK;
+    CN_REQUIRE(rgb && out, CN_ERR_ARG, "cn_rgb8_pack: null pointer");
+    CN_REQUIRE(((uintptr_t)rgb & 3) == 0, CN_ERR_ALIGN, "cn_rgb8_pack: alignment");
+    rgb8_pack_kernel<<<stride_blocks(n), 256, 0, (hipStream_t)stream>>>(n, rgb, out);
+    return check_launch("cn_rgb8_pack");
 }

@@ -1,6 +1,9 @@
 // cn_mesh.hip — mesh extraction (ABI v16): the grid points of a bounding box, the SDF volume over them
 // (cn_grid_points + cn_sdf_query in row chunks) and the isosurface of a volume as a welded triangle mesh
-// by marching tetrahedra on the six-tetrahedron Kuhn split (cn_mesh_count / cn_mesh_emit).
+// by marching tetrahedra on the six-tetrahedron Kuhn split (cn_mesh_count / cn_mesh_emit); and floater removal
+// on any indexed triangle list: connected components by label propagation with pointer jumping
+// (cn_mesh_label_init / cn_mesh_label_rounds), the triangles per component (cn_mesh_component_sizes) and the
+// compaction to the kept components through the mesher's scans (cn_mesh_select / cn_mesh_compact).
 //
 // Reference: NeuSRenderer.extract_geometry / extract_fields (neus_renderer.py:10-37): the interface and the
 // grid (torch.linspace per axis, u[xi, yi, zi], vertices / (resolution - 1) * (max - min) + min).  The
@@ -387,6 +390,216 @@ int scan_launch(const char* who, const uint8_t* c, int n, int tiles, int32_t* to
     return check_launch(who);
 }
 
+// -- connected components of an indexed triangle list, and its compaction to the kept ones -----------------
+// Labels are vertex ids of the vertex's own component and only ever fall (atomicMin, or a jump to a label
+// that is itself a lower id), so whatever order the atomics land in, the only fixed point is the smallest id
+// of every component.  A round is two launches; nothing waits for another workgroup.
+struct CleanArgs {
+    int V, T;
+    const int32_t* tri;
+    int32_t* label;
+    int32_t* tri_count;
+    int keep_largest, min_triangles;
+    uint8_t* vflag;     // [V] 1: the vertex's component is kept
+    int32_t* voff;      // [V] exclusive scan of vflag
+    uint8_t* tflag;     // [T]
+    int32_t* toff;      // [T]
+    uint64_t* best;     // the largest component: (triangles << 32) | ~root
+    const int64_t* counts;
+    int32_t* kept_vertices;
+    int32_t* tri_out;
+    int64_t max_vertices, max_triangles;
+};
+
+__device__ __forceinline__ int label_at(const int32_t* label, int v) {
+    return __atomic_load_n(label + v, __ATOMIC_RELAXED);  // (other threads lower it meanwhile)
+}
+
+__global__ void label_init_kernel(int V, int32_t* __restrict__ label) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v < V) label[v] = v;
+}
+
+__global__ void clear_flag_kernel(int32_t* changed) { *changed = 0; }
+
+__global__ void label_hook_kernel(int V, int T, const int32_t* __restrict__ tri, int32_t* label, int32_t* changed) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= T) return;
+    int c[3], l[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        c[j] = tri[(int64_t)t * 3 + j];
+        if ((unsigned)c[j] >= (unsigned)V) return;  // an index outside the vertex list joins nothing
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) l[j] = label_at(label, c[j]);
+    const int m = min(l[0], min(l[1], l[2]));
+    bool lowered = false;
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+        if (l[j] > m) lowered |= atomicMin(label + c[j], m) > m;
+    if (lowered) *changed = 1;
+}
+
+__global__ void label_jump_kernel(int V, int32_t* label, int32_t* changed) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= V) return;
+    const int l = label_at(label, v);
+    if ((unsigned)l >= (unsigned)V) return;  // (never after cn_mesh_label_init: labels start as ids and fall to ids)
+    const int ll = label_at(label, l);
+    if (ll < l) {
+        atomicMin(label + v, ll);
+        *changed = 1;
+    }
+}
+
+__global__ void zero_i32_kernel(int n, int32_t* __restrict__ p) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = 0;
+}
+
+// root of triangle t: the label of its first corner, or -1 where that index is outside the vertex list
+__device__ __forceinline__ int tri_root(const CleanArgs& a, int t) {
+    const int c = a.tri[(int64_t)t * 3];
+    return (unsigned)c < (unsigned)a.V ? a.label[c] : -1;
+}
+
+__global__ void component_sizes_kernel(CleanArgs a) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= a.T) return;
+    const int r = tri_root(a, t);
+    if ((unsigned)r < (unsigned)a.V) atomicAdd(a.tri_count + r, 1);
+}
+
+__global__ void best_clear_kernel(uint64_t* best) { *best = 0; }
+
+// the largest component, a tie to the smaller root: the maximum of (count, ~root) does not depend on the order
+__global__ void best_component_kernel(CleanArgs a) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= a.V) return;
+    const int n = a.tri_count[v];
+    if (n > 0) atomicMax((unsigned long long*)a.best, ((unsigned long long)n << 32) | (uint32_t)~(uint32_t)v);
+}
+
+__device__ __forceinline__ bool root_kept(const CleanArgs& a, int r) {
+    if ((unsigned)r >= (unsigned)a.V) return false;
+    const int n = a.tri_count[r];
+    if (n < a.min_triangles) return false;
+    if (!a.keep_largest) return true;
+    const uint64_t b = *a.best;
+    return b != 0 && (uint32_t)~(uint32_t)b == (uint32_t)r;
+}
+
+// one thread per index of max(V, T): the vertex's flag and the triangle's
+__global__ void select_flags_kernel(CleanArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < a.V) a.vflag[i] = root_kept(a, a.label[i]) ? 1 : 0;
+    if (i < a.T) a.tflag[i] = root_kept(a, tri_root(a, i)) ? 1 : 0;
+}
+
+__global__ void compact_kernel(CleanArgs a) {
+    // output buffers smaller than the counts: nothing is written (the decision is the same in every thread)
+    if (a.counts[0] > a.max_vertices || a.counts[1] > a.max_triangles) return;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < a.V && a.vflag[i]) {
+        const int o = a.voff[i];
+        if (o < a.max_vertices) a.kept_vertices[o] = i;
+    }
+    if (i < a.T && a.tflag[i]) {
+        const int64_t o = a.toff[i];
+        if (o >= a.max_triangles) return;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            // (a kept triangle's corners share its component only in a well-formed list: an index outside the
+            // vertex list, or a corner that was not kept, is written as -1, never read out of bounds)
+            const int c = a.tri[(int64_t)i * 3 + j];
+            a.tri_out[o * 3 + j] = ((unsigned)c < (unsigned)a.V && a.vflag[c]) ? a.voff[c] : -1;
+        }
+    }
+}
+
+struct CleanPlan {
+    uint8_t* vflag;
+    uint8_t* tflag;
+    int32_t* voff;
+    int32_t* toff;
+    int32_t* vtot;
+    int32_t* ttot;
+    uint64_t* best;
+    int vt, tt;
+    size_t bytes;
+};
+
+CleanPlan clean_plan(int V, int T, void* ws) {
+    CleanPlan p{};
+    p.vt = V ? (V + kScanTile - 1) / kScanTile : 1;
+    p.tt = T ? (T + kScanTile - 1) / kScanTile : 1;
+    char* b = static_cast<char*>(ws);
+    size_t used = 0;
+    auto take = [&](size_t n) {
+        char* q = b ? b + used : nullptr;
+        used += rup_sz(n);
+        return q;
+    };
+    p.vflag = reinterpret_cast<uint8_t*>(take((size_t)V));
+    p.tflag = reinterpret_cast<uint8_t*>(take((size_t)T));
+    p.voff = reinterpret_cast<int32_t*>(take((size_t)V * 4));
+    p.toff = reinterpret_cast<int32_t*>(take((size_t)T * 4));
+    p.vtot = reinterpret_cast<int32_t*>(take((size_t)p.vt * 4));
+    p.ttot = reinterpret_cast<int32_t*>(take((size_t)p.tt * 4));
+    p.best = reinterpret_cast<uint64_t*>(take(8));
+    p.bytes = used;
+    return p;
+}
+
+// the descriptor's sizes and the pointers every entry reads
+int clean_check(const char* who, const cn_mesh_clean_desc* d, bool need_label) {
+    CN_REQUIRE(d, CN_ERR_ARG, "%s: null descriptor", who);
+    CN_REQUIRE(d->V >= 0 && d->T >= 0, CN_ERR_SHAPE, "%s: V %d, T %d", who, d->V, d->T);
+    CN_REQUIRE(d->T == 0 || d->triangles, CN_ERR_ARG, "%s: null triangles", who);
+    CN_REQUIRE(!need_label || d->V == 0 || d->label, CN_ERR_ARG, "%s: null label", who);
+    CN_REQUIRE(((uintptr_t)d->triangles & 3) == 0 && ((uintptr_t)d->label & 3) == 0, CN_ERR_ALIGN,
+               "%s: triangles / label 4-byte aligned", who);
+    return CN_OK;
+}
+
+int clean_ws_check(const char* who, const cn_mesh_clean_desc* d, const void* ws, int64_t ws_bytes) {
+    int rc = clean_check(who, d, true);
+    if (rc) return rc;
+    CN_REQUIRE(d->V == 0 || d->tri_count, CN_ERR_ARG, "%s: null tri_count", who);
+    CN_REQUIRE(d->counts, CN_ERR_ARG, "%s: null counts", who);
+    CN_REQUIRE(((uintptr_t)d->tri_count & 3) == 0 && ((uintptr_t)d->counts & 7) == 0, CN_ERR_ALIGN,
+               "%s: tri_count 4-byte, counts 8-byte aligned", who);
+    CN_REQUIRE(d->min_triangles >= 0, CN_ERR_SHAPE, "%s: min_triangles %d", who, d->min_triangles);
+    const size_t need = clean_plan(d->V, d->T, nullptr).bytes;
+    CN_REQUIRE(ws && ws_bytes >= 0 && (size_t)ws_bytes >= need, CN_ERR_SHAPE, "%s: workspace %lld bytes, %zu needed", who,
+               (long long)ws_bytes, need);
+    CN_REQUIRE(((uintptr_t)ws & (kAlign - 1)) == 0, CN_ERR_ALIGN, "%s: workspace not 256-byte aligned", who);
+    return CN_OK;
+}
+
+CleanArgs clean_args(const cn_mesh_clean_desc* d, const CleanPlan& p) {
+    CleanArgs a{};
+    a.V = d->V;
+    a.T = d->T;
+    a.tri = d->triangles;
+    a.label = d->label;
+    a.tri_count = d->tri_count;
+    a.keep_largest = d->keep_largest;
+    a.min_triangles = d->min_triangles;
+    a.vflag = p.vflag;
+    a.voff = p.voff;
+    a.tflag = p.tflag;
+    a.toff = p.toff;
+    a.best = p.best;
+    a.counts = d->counts;
+    a.kept_vertices = d->kept_vertices;
+    a.tri_out = d->triangles_out;
+    a.max_vertices = d->max_vertices;
+    a.max_triangles = d->max_triangles;
+    return a;
+}
+
 }  // namespace
 }  // namespace cn
 
@@ -488,4 +701,84 @@ extern "C" int cn_mesh_emit(const cn_mesh_desc* d, void* workspace, int64_t work
     const MeshArgs a = mesh_args(d, p);
     mesh_emit_kernel<<<(p.N + 255) / 256, 256, 0, (hipStream_t)stream>>>(a);
     return check_launch("cn_mesh_emit");
+}
+
+extern "C" int cn_mesh_label_init(const cn_mesh_clean_desc* d, cn_stream_t stream) {
+    int rc = clean_check("cn_mesh_label_init", d, true);
+    if (rc || d->V == 0) return rc;
+    label_init_kernel<<<(d->V + 255) / 256, 256, 0, (hipStream_t)stream>>>(d->V, d->label);
+    return check_launch("cn_mesh_label_init");
+}
+
+extern "C" int cn_mesh_label_rounds(const cn_mesh_clean_desc* d, int32_t k, int32_t* changed, cn_stream_t stream) {
+    int rc = clean_check("cn_mesh_label_rounds", d, true);
+    if (rc) return rc;
+    CN_REQUIRE(k >= 1, CN_ERR_SHAPE, "cn_mesh_label_rounds: k %d", k);
+    CN_REQUIRE(changed, CN_ERR_ARG, "cn_mesh_label_rounds: null changed");
+    CN_REQUIRE(((uintptr_t)changed & 3) == 0, CN_ERR_ALIGN, "cn_mesh_label_rounds: changed 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    clear_flag_kernel<<<1, 1, 0, st>>>(changed);
+    if ((rc = check_launch("cn_mesh_label_rounds"))) return rc;
+    if (d->V == 0 || d->T == 0) return CN_OK;
+    for (int i = 0; i < k; ++i) {
+        label_hook_kernel<<<(d->T + 255) / 256, 256, 0, st>>>(d->V, d->T, d->triangles, d->label, changed);
+        if ((rc = check_launch("cn_mesh_label_rounds"))) return rc;
+        label_jump_kernel<<<(d->V + 255) / 256, 256, 0, st>>>(d->V, d->label, changed);
+        if ((rc = check_launch("cn_mesh_label_rounds"))) return rc;
+    }
+    return CN_OK;
+}
+
+extern "C" int cn_mesh_component_sizes(const cn_mesh_clean_desc* d, cn_stream_t stream) {
+    int rc = clean_check("cn_mesh_component_sizes", d, true);
+    if (rc || d->V == 0) return rc;
+    CN_REQUIRE(d->tri_count, CN_ERR_ARG, "cn_mesh_component_sizes: null tri_count");
+    CN_REQUIRE(((uintptr_t)d->tri_count & 3) == 0, CN_ERR_ALIGN, "cn_mesh_component_sizes: tri_count 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    zero_i32_kernel<<<(d->V + 255) / 256, 256, 0, st>>>(d->V, d->tri_count);
+    if ((rc = check_launch("cn_mesh_component_sizes")) || d->T == 0) return rc;
+    component_sizes_kernel<<<(d->T + 255) / 256, 256, 0, st>>>(clean_args(d, CleanPlan{}));
+    return check_launch("cn_mesh_component_sizes");
+}
+
+extern "C" size_t cn_mesh_clean_workspace_bytes(int32_t V, int32_t T) {
+    if (V < 0 || T < 0) return 0;
+    return clean_plan(V, T, nullptr).bytes;
+}
+
+extern "C" int cn_mesh_select(const cn_mesh_clean_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream) {
+    int rc = clean_ws_check("cn_mesh_select", d, workspace, workspace_bytes);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const CleanPlan p = clean_plan(d->V, d->T, workspace);
+    const CleanArgs a = clean_args(d, p);
+    best_clear_kernel<<<1, 1, 0, st>>>(p.best);
+    if ((rc = check_launch("cn_mesh_select"))) return rc;
+    if (d->keep_largest && d->V > 0) {
+        best_component_kernel<<<(d->V + 255) / 256, 256, 0, st>>>(a);
+        if ((rc = check_launch("cn_mesh_select"))) return rc;
+    }
+    const int n = d->V > d->T ? d->V : d->T;
+    if (n > 0) {
+        select_flags_kernel<<<(n + 255) / 256, 256, 0, st>>>(a);
+        if ((rc = check_launch("cn_mesh_select"))) return rc;
+    }
+    // (an empty list scans one empty tile: the counts are written as zeros)
+    if ((rc = scan_launch<false>("cn_mesh_select", p.vflag, d->V, p.vt, p.vtot, p.voff, d->counts, st))) return rc;
+    return scan_launch<false>("cn_mesh_select", p.tflag, d->T, p.tt, p.ttot, p.toff, d->counts + 1, st);
+}
+
+extern "C" int cn_mesh_compact(const cn_mesh_clean_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream) {
+    int rc = clean_ws_check("cn_mesh_compact", d, workspace, workspace_bytes);
+    if (rc) return rc;
+    CN_REQUIRE(d->max_vertices >= 0 && d->max_triangles >= 0, CN_ERR_SHAPE, "cn_mesh_compact: max_vertices %lld / max_triangles %lld",
+               (long long)d->max_vertices, (long long)d->max_triangles);
+    CN_REQUIRE((d->max_vertices == 0 || d->kept_vertices) && (d->max_triangles == 0 || d->triangles_out), CN_ERR_ARG,
+               "cn_mesh_compact: null kept_vertices / triangles_out");
+    CN_REQUIRE(((uintptr_t)d->kept_vertices & 3) == 0 && ((uintptr_t)d->triangles_out & 3) == 0, CN_ERR_ALIGN,
+               "cn_mesh_compact: kept_vertices / triangles_out 4-byte aligned");
+    const int n = d->V > d->T ? d->V : d->T;
+    if (n == 0) return CN_OK;
+    compact_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(clean_args(d, clean_plan(d->V, d->T, workspace)));
+    return check_launch("cn_mesh_compact");
 }

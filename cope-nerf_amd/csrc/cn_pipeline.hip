@@ -792,24 +792,29 @@ int color_field_plan(const cn_color_net* c, const ColorShape& s, int M, const fl
     return cn_row_head(M, c->in_dim[n - 1], last, HL, c->head_w, c->in_dim[n - 1], c->head_b, 3, 1, rgb, 3, nullptr, st);
 }
 
-int render_check(const cn_render_desc* d, NetShape* s, ColorShape* cs, bool train = false) {
-    CN_REQUIRE(d, CN_ERR_ARG, "cn_render_fwd: null descriptor");
-    int rc = net_shape(d->sdf_net, s);
+// What the field part of the rendering forward (sdf_field_plan + color_field_plan) asks of the two networks
+int fold_check(const char* who, const cn_sdf_net* n, const cn_color_net* c, NetShape* s, ColorShape* cs) {
+    int rc = net_shape(n, s);
     if (rc) return rc;
-    if ((rc = color_shape(d->color_net, cs))) return rc;
-    const cn_sdf_net* n = d->sdf_net;
-    const cn_color_net* c = d->color_net;
-    CN_REQUIRE(n->mfma_dtype == c->mfma_dtype, CN_ERR_ARG, "cn_render_fwd: the networks' GEMM modes differ");
+    if ((rc = color_shape(c, cs))) return rc;
+    CN_REQUIRE(n->mfma_dtype == c->mfma_dtype, CN_ERR_ARG, "%s: the networks' GEMM modes differ", who);
     // the folded feature head (copenerf.renderer's fold): the colour network reads the SDF's last hidden layer
     CN_REQUIRE(n->in_dim[s->L8] == s->HL && s->HL == c->d_feature && n->out_dim[s->L8] == 1 + c->d_feature,
-               CN_ERR_UNSUPPORTED, "cn_render_fwd: needs the folded feature head (SDF hidden width == d_feature)");
+               CN_ERR_UNSUPPORTED, "%s: needs the folded feature head (SDF hidden width == d_feature)", who);
     for (int l = 0; l < s->L8; ++l) {
         const int kq = s->bf ? 64 : 32;
         CN_REQUIRE(n->Wt[l] && ((uintptr_t)n->Wt[l] & 15) == 0 && n->wt_rows[l] >= rup_i(n->in_dim[l], 128) &&
                        n->wt_cols[l] >= rup_i(n->out_dim[l], kq),
-                   CN_ERR_SHAPE, "cn_render_fwd: transposed image %d missing or too small", l);
+                   CN_ERR_SHAPE, "%s: transposed image %d missing or too small", who, l);
     }
-    CN_REQUIRE(n->head_wp && ((uintptr_t)n->head_wp & 15) == 0, CN_ERR_ALIGN, "cn_render_fwd: head_wp [HL] (16-byte aligned)");
+    CN_REQUIRE(n->head_wp && ((uintptr_t)n->head_wp & 15) == 0, CN_ERR_ALIGN, "%s: head_wp [HL] (16-byte aligned)", who);
+    return CN_OK;
+}
+
+int render_check(const cn_render_desc* d, NetShape* s, ColorShape* cs, bool train = false) {
+    CN_REQUIRE(d, CN_ERR_ARG, "cn_render_fwd: null descriptor");
+    int rc = fold_check("cn_render_fwd", d->sdf_net, d->color_net, s, cs);
+    if (rc) return rc;
     CN_REQUIRE(d->R >= 0 && d->rays_o && d->rays_d && d->near && d->far && d->time_step && d->inv_s &&
                    d->cos_anneal_ratio,
                CN_ERR_ARG, "cn_render_fwd: null input");
@@ -909,6 +914,129 @@ extern "C" int cn_render_fwd(const cn_render_desc* d, void* workspace, int64_t w
         return rc;
     return cn_composite_fwd(R, S, d->z, d->sdf, d->grad, 4, d->rgb, d->rays_d, d->inv_s, d->near, d->far, d->n_samples,
                             d->cos_anneal_ratio, d->color, d->depth, d->weights, d->cdf, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// cn_point_colors: the colour network at surface points (vertex colours of an extracted mesh), the view
+// direction the inward unit normal -- NeuSRenderer.vertex_colors' composition (SDFNetwork.field with the
+// hidden activation and ∇ₓSDF, ops.vertex_dirs, RenderingNetwork.color with dir_div 1) in row chunks: the
+// field part of cn_render_fwd at points the caller gives, the same launches, the same bits.
+namespace {
+
+constexpr int32_t kColorChunk = 1 << 18;
+
+// pts [M][4] = (x[m], t): the rows torch.cat([x, t.expand(M, 1)], 1) holds; dirs [M][3] = one fixed row
+__global__ void __launch_bounds__(256) point_rows_kernel(int M, const float* __restrict__ x, const float* __restrict__ t,
+                                                         float* __restrict__ pts, float vx, float vy, float vz,
+                                                         float* __restrict__ dirs) {
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    if (m >= M) return;
+    cn::floatx4 o;
+    o[0] = x[3 * (int64_t)m];
+    o[1] = x[3 * (int64_t)m + 1];
+    o[2] = x[3 * (int64_t)m + 2];
+    o[3] = t[0];
+    reinterpret_cast<cn::floatx4*>(pts)[m] = o;
+    if (dirs) {
+        dirs[3 * (int64_t)m] = vx;
+        dirs[3 * (int64_t)m + 1] = vy;
+        dirs[3 * (int64_t)m + 2] = vz;
+    }
+}
+
+struct ColorsPlan {
+    float* pts;
+    float* sdf;
+    float* G;
+    float* dirs;
+};
+
+// one chunk of Mc rows: its own buffers, then the two networks' (run: launch; else size only)
+int point_colors_chunk(const cn_point_colors_desc* d, const NetShape& s, const ColorShape& cs, int Mc, int64_t m0,
+                       const float* vd, Plan& ws, hipStream_t st, bool run) {
+    ColorsPlan p;
+    p.pts = static_cast<float*>(ws.take((size_t)Mc * 16));
+    p.sdf = static_cast<float*>(ws.take((size_t)Mc * 4));
+    p.G = static_cast<float*>(ws.take((size_t)Mc * 16));  // (also when grad is given: the plan does not depend on it)
+    p.dirs = static_cast<float*>(ws.take((size_t)Mc * 12));
+    float* G = run && d->grad ? d->grad + 4 * m0 : p.G;
+    float* rgb = run ? d->rgb + 3 * m0 : nullptr;
+    int rc;
+    if (run) {
+        point_rows_kernel<<<(Mc + 255) / 256, 256, 0, st>>>(Mc, d->x + 3 * m0, d->time_step, p.pts, vd ? vd[0] : 0.0f,
+                                                             vd ? vd[1] : 0.0f, vd ? vd[2] : 0.0f,
+                                                             vd ? p.dirs : nullptr);
+        if ((rc = cn::check_launch("cn_point_colors"))) return rc;
+    }
+    float* U8 = nullptr;
+    if ((rc = sdf_field_plan(d->sdf_net, s, Mc, p.pts, p.sdf, &U8, G, ws, st, run))) return rc;
+    if (run && !vd && (rc = cn_vertex_dirs(Mc, G, 4, -1.0f, p.dirs, st))) return rc;
+    if ((rc = color_field_plan(d->color_net, cs, Mc, G, p.pts, p.dirs, 1, U8, s.HL, rgb, ws, st, run))) return rc;
+    if (run && d->rgb8) return cn_rgb8_pack((int64_t)Mc * 3, rgb, d->rgb8 + 3 * m0, st);
+    return CN_OK;
+}
+
+int point_colors_check(const cn_point_colors_desc* d, NetShape* s, ColorShape* cs, int32_t* chunk) {
+    CN_REQUIRE(d, CN_ERR_ARG, "cn_point_colors: null descriptor");
+    int rc = fold_check("cn_point_colors", d->sdf_net, d->color_net, s, cs);
+    if (rc) return rc;
+    CN_REQUIRE(d->M >= 0 && d->chunk_rows >= 0, CN_ERR_SHAPE, "cn_point_colors: M %lld, chunk_rows %d", (long long)d->M,
+               d->chunk_rows);
+    const int64_t c = d->chunk_rows ? d->chunk_rows : kColorChunk;
+    *chunk = (int32_t)(c < d->M ? c : d->M);
+    // every buffer of a chunk is addressed with 32-bit element offsets: the widest row bounds the chunk
+    int row = s->HL > cs->HL ? s->HL : cs->HL;
+    row = row > s->KE ? row : s->KE;
+    row = row > cs->KX ? row : cs->KX;
+    CN_REQUIRE((int64_t)*chunk * row * 4 < ((int64_t)1 << 31), CN_ERR_SHAPE,
+               "cn_point_colors: a chunk of %d rows x %d bytes reaches 2^31 (lower chunk_rows)", *chunk, row * 4);
+    return CN_OK;
+}
+
+}  // namespace
+
+extern "C" size_t cn_point_colors_workspace_bytes(const cn_point_colors_desc* d) {
+    NetShape s;
+    ColorShape cs;
+    int32_t chunk;
+    if (point_colors_check(d, &s, &cs, &chunk) != CN_OK) return 0;
+    Plan ws(nullptr);
+    point_colors_chunk(d, s, cs, chunk, 0, nullptr, ws, nullptr, false);
+    return ws.used;
+}
+
+extern "C" int cn_point_colors(const cn_point_colors_desc* d, void* workspace, int64_t workspace_bytes,
+                               cn_stream_t stream) {
+    NetShape s;
+    ColorShape cs;
+    int32_t chunk;
+    int rc = point_colors_check(d, &s, &cs, &chunk);
+    if (rc) return rc;
+    float vd[3];
+    if (d->view_dir) {
+        const double x = d->view_dir[0], y = d->view_dir[1], z = d->view_dir[2];
+        const double n = std::sqrt((x * x + y * y) + z * z);
+        CN_REQUIRE(n > 0.0 && std::isfinite(n), CN_ERR_ARG, "cn_point_colors: view_dir (%g, %g, %g) has no direction", x,
+                   y, z);
+        vd[0] = (float)(x / n);
+        vd[1] = (float)(y / n);
+        vd[2] = (float)(z / n);
+    }
+    if (d->M == 0) return CN_OK;
+    CN_REQUIRE(d->x && d->time_step && d->rgb, CN_ERR_ARG, "cn_point_colors: null x / time_step / rgb");
+    CN_REQUIRE(((uintptr_t)d->x & 3) == 0 && ((uintptr_t)d->rgb & 3) == 0 && ((uintptr_t)d->grad & 15) == 0, CN_ERR_ALIGN,
+               "cn_point_colors: x / rgb 4-byte, grad 16-byte aligned");
+    const size_t need = cn_point_colors_workspace_bytes(d);
+    CN_REQUIRE(workspace && workspace_bytes >= 0 && (size_t)workspace_bytes >= need, CN_ERR_SHAPE,
+               "cn_point_colors: workspace %lld bytes, %zu needed", (long long)workspace_bytes, need);
+    CN_REQUIRE(((uintptr_t)workspace & (kAlign - 1)) == 0, CN_ERR_ALIGN, "cn_point_colors: workspace not 256-byte aligned");
+    for (int64_t m0 = 0; m0 < d->M; m0 += chunk) {
+        const int Mc = (int)(d->M - m0 < chunk ? d->M - m0 : chunk);
+        Plan ws(workspace);
+        if ((rc = point_colors_chunk(d, s, cs, Mc, m0, d->view_dir ? vd : nullptr, ws, (hipStream_t)stream, true)))
+            return rc;
+    }
+    return CN_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -858,6 +858,99 @@ int cn_mesh_count(const cn_mesh_desc* d, void* workspace, int64_t workspace_byte
 int cn_mesh_emit(const cn_mesh_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * Vertex colours (additive to ABI v22): the colour network at surface points, with the
+ * view direction set to the inward unit normal of every point (the usual convention of
+ * NeuS-family exporters; the reference's extract_geometry stops at the geometry).
+ *
+ * cn_vertex_dirs: dirs [M][3] = sign * G[m][0:3] / max(|G[m][0:3]|, 1e-12) for rows
+ * G [M][ldg >= 3] (the first three columns of ∇ₓSDF), the norm
+ * sqrtf((gx gx + gy gy) + gz gz) without FMA contraction; one thread per row.  A zero row
+ * gives exact zeros.
+ *
+ * cn_rgb8_pack: out[i] = floorf(fminf(fmaxf(rgb[i], 0), 1) * 255 + 0.5) as uint8 for n
+ * values, NaN -> 0.
+ *
+ * cn_point_colors: rgb [M][3] = RenderingNetwork(x, t, dir, ∇ₓSDF, feature) at the DEVICE
+ * points x [M][3] and the device scalar time_step, dir = -n̂ (cn_vertex_dirs, sign -1) or,
+ * with view_dir != NULL (HOST float [3], read during the call, not zero), the row
+ * (float)(v / |v|) (the quotient in double, |v| = sqrt((x x + y y) + z z)) on every point.
+ * Per chunk of chunk_rows rows (0: 2^18): the rows (x, t), the SDF field with its ∇ₓSDF
+ * pass, cn_vertex_dirs (or the fixed row), the colour network with dir_div = 1 -- the
+ * launches of cn_render_fwd's field part, so the networks must satisfy its conditions (the
+ * folded feature head: CN_ERR_UNSUPPORTED otherwise; equal GEMM modes) and the results are
+ * bitwise copenerf's composition SDFNetwork.field / ops.vertex_dirs / RenderingNetwork.color,
+ * the same for every chunk_rows.  Optional outputs: rgb8 [M][3] (cn_rgb8_pack of rgb) and
+ * grad [M][4] (∇ₓSDF, 16-byte aligned).  M = 0 writes nothing.  A chunk of
+ * chunk x (widest buffer row) bytes >= 2^31 is CN_ERR_SHAPE before anything launches.
+ * Workspace (256-byte aligned): cn_point_colors_workspace_bytes (one chunk's rows, sdf,
+ * ∇ₓSDF, dirs and the two networks' buffers; 0 for a descriptor the call would refuse).
+ * ------------------------------------------------------------------------ */
+int cn_vertex_dirs(int64_t M, const float* G, int64_t ldg, float sign, float* dirs, cn_stream_t stream);
+int cn_rgb8_pack(int64_t n, const float* rgb, uint8_t* out, cn_stream_t stream);
+typedef struct cn_point_colors_desc {
+    int64_t M;
+    const float* x;                     /* [M][3] */
+    const float* time_step;             /* device [1] */
+    const cn_sdf_net* sdf_net;
+    const cn_color_net* color_net;
+    const float* view_dir;              /* HOST [3], or NULL: the inward normals */
+    int32_t chunk_rows;
+    float* rgb;                         /* [M][3] */
+    uint8_t* rgb8;                      /* [M][3], or NULL */
+    float* grad;                        /* [M][4], or NULL */
+} cn_point_colors_desc;
+size_t cn_point_colors_workspace_bytes(const cn_point_colors_desc* d);
+int cn_point_colors(const cn_point_colors_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
+ * Connected components of a welded indexed triangle list and its compaction to the kept
+ * components (additive to ABI v22): floater removal without leaving the device.  triangles
+ * [T][3] are DEVICE int32 indices into V vertices (any such list, the mesher's or not).
+ *
+ * cn_mesh_label_init: label[v] = v.  cn_mesh_label_rounds: *changed = 0, then k rounds of
+ *   (1) every triangle takes the minimum label of its corners and atomicMins it into all
+ *       three, (2) every vertex jumps, label[v] = label[label[v]];
+ * a round that lowers any label sets *changed (DEVICE int32) to 1.  Labels only fall and
+ * stay vertex ids of the vertex's own component, so the fixed point -- every vertex holds
+ * the smallest vertex id of its component -- is unique and does not depend on the order
+ * of the atomics.  No kernel waits for another workgroup: the caller repeats the call
+ * until *changed reads 0 (a host read; at most V rounds are ever needed, since round r
+ * reaches every vertex within r edges of its component's smallest id).
+ * cn_mesh_component_sizes: tri_count [V] = the triangles of every component at its root
+ * id (the label of a triangle's first corner), 0 elsewhere; integer atomics, exact.
+ * cn_mesh_select: a component is kept if it has at least min_triangles triangles and,
+ * with keep_largest, is the one with the most triangles (a tie goes to the smaller root
+ * id; none when T = 0).  Writes counts = (V', T') (DEVICE int64 [2]: the vertices whose
+ * component is kept, the triangles whose first corner's is) and leaves the 0/1 flags and
+ * their exclusive scans in the workspace.  cn_mesh_compact, with the same descriptor and
+ * workspace, writes kept_vertices [V'] (the original ids, ascending) and triangles_out
+ * [T'][3] (renumbered, in their original order); like cn_mesh_emit it checks
+ * max_vertices / max_triangles against the device counts and writes nothing at all into
+ * buffers that are too small.
+ * Workspace (256-byte aligned), every piece rounded up to 256 bytes: V + T (flags) + 4 V
+ * + 4 T (offsets) + 4 max(1, ceil(V / 1024)) + 4 max(1, ceil(T / 1024)) (the scans' tile
+ * totals) + 8 (the largest component).  V < 0 or T < 0: CN_ERR_SHAPE (workspace_bytes: 0).
+ * ------------------------------------------------------------------------ */
+typedef struct cn_mesh_clean_desc {
+    int32_t V, T;
+    const int32_t* triangles;           /* [T][3] */
+    int32_t* label;                     /* [V] */
+    int32_t* tri_count;                 /* [V] -- cn_mesh_component_sizes, read by cn_mesh_select */
+    int32_t keep_largest, min_triangles;
+    int64_t* counts;                    /* device [2]: V', T' */
+    int32_t* kept_vertices;             /* [max_vertices] -- cn_mesh_compact */
+    int64_t max_vertices;
+    int32_t* triangles_out;             /* [max_triangles][3] -- cn_mesh_compact */
+    int64_t max_triangles;
+} cn_mesh_clean_desc;
+int cn_mesh_label_init(const cn_mesh_clean_desc* d, cn_stream_t stream);
+int cn_mesh_label_rounds(const cn_mesh_clean_desc* d, int32_t k, int32_t* changed, cn_stream_t stream);
+int cn_mesh_component_sizes(const cn_mesh_clean_desc* d, cn_stream_t stream);
+size_t cn_mesh_clean_workspace_bytes(int32_t V, int32_t T);
+int cn_mesh_select(const cn_mesh_clean_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+int cn_mesh_compact(const cn_mesh_clean_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * Pose refinement (ABI v17): compute_loss_and_warp_image
  * (utils_poses/pose_refinement.py:34-61) for J (target, source) jobs over one image
  * stack, with the pose gradient in the same pass -- the per-batch work of

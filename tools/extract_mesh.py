@@ -2,10 +2,12 @@
 
     python tools/extract_mesh.py CHECKPOINT OUT.ply [--bound-min X Y Z] [--bound-max X Y Z]
         [--resolution N] [--threshold S] [--time T] [--mode fp32|bf16x6|bf16] [--normals]
+        [--colors [--view-dir X Y Z]] [--keep-largest] [--min-triangles N]
 
 The checkpoint is one train.py wrote through CheckpointIO (a DataParallel NeuSRenderer under "model", reference
 or this build); the network widths are read from its shapes.  NeuSRenderer.extract_geometry does the work:
-the SDF volume and the marching-tetrahedra mesher run on the device."""
+the SDF volume, the marching-tetrahedra mesher, floater removal (--keep-largest, --min-triangles) and the vertex
+colours (--colors) run on the device."""
 import argparse
 import os
 import sys
@@ -46,14 +48,27 @@ def main(argv=None):
     ap.add_argument("--time", type=float, default=0.0, help="the time value t of the (x, y, z, t) SDF")
     ap.add_argument("--mode", choices=["fp32", "bf16x6", "bf16"], default="bf16x6", help="the MLP GEMMs' MFMA mode")
     ap.add_argument("--normals", action="store_true", help="also write unit normals (the SDF's gradient)")
+    ap.add_argument("--colors", action="store_true",
+                    help="also write 8-bit vertex colours (the colour network seen along the inward normal)")
+    ap.add_argument("--view-dir", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"),
+                    help="with --colors: one fixed view direction for every vertex instead of the inward normal")
+    ap.add_argument("--keep-largest", action="store_true",
+                    help="keep only the connected component with the most triangles")
+    ap.add_argument("--min-triangles", type=int, default=0, metavar="N",
+                    help="drop every connected component with fewer than N triangles")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("extract_mesh: needs a HIP device (the kernels have no CPU fallback)")
     r = build_renderer(a.checkpoint).to("cuda").set_mfma_dtype(a.mode)
+    stats = {}
     res = r.extract_geometry(torch.tensor(a.bound_min), torch.tensor(a.bound_max), a.resolution, a.threshold,
-                             time_step=a.time, with_normals=a.normals)
-    write_ply(a.out, res[0], res[1], normals=res[2] if a.normals else None)
-    print(f"{a.out}: {len(res[0])} vertices, {len(res[1])} triangles")
+                             time_step=a.time, with_normals=a.normals, with_colors=a.colors, view_dir=a.view_dir,
+                             keep_largest=a.keep_largest, min_triangles=a.min_triangles, stats=stats)
+    write_ply(a.out, res[0], res[1], normals=res[2] if a.normals else None, colors=res[-1] if a.colors else None)
+    line = f"{a.out}: {len(res[0])} vertices, {len(res[1])} triangles"
+    if stats:
+        line += f", {stats['components']} components found, {stats['components_kept']} kept"
+    print(line)
     return res
 
 

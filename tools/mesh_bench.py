@@ -1,7 +1,10 @@
 """Mesh extraction timings on the device: cn_sdf_grid and the mesher's two passes (cn_mesh_count, cn_mesh_emit)
 at 256^3 and 512^3 with the C2 network (d_hidden 256) in bf16x6, against the reference-shaped baseline built
 from the product API (extract_fields, neus_renderer.py:10-25: 64^3 blocks through SDFNetwork.sdf with a host copy
-per block).
+per block); and, on the extracted mesh, the colour pass (one cn_point_colors call next to the chunked module
+composition with the same packs: the same launches, so this measures the per-chunk Python loop, nothing else) and the
+clean pass (ops.mesh_clean keep_largest, host clock: it reads the `changed` flag and the counts back).  With --out
+the colour and clean figures also go to DIR/mesh_color_bench.json (profiles/mesh_color_bench.json is one such run).
 
     python tools/mesh_bench.py [--res 256 512] [--repeats 7] [--out DIR]
 
@@ -95,10 +98,13 @@ def main(argv=None):
     stamp = open(stamp_path).read().strip()[:12] if os.path.exists(stamp_path) else "unstamped"
     dev = torch.device("cuda")
     t = ops.device_scalar(a.time, dev)
-    rows = []
+    rows, color_rows = [], []
     with torch.no_grad():
-        pk = r.sdf_network.params_and_pack()[2]
+        sdf_packed = r.sdf_network.params_and_pack()
+        pk = sdf_packed[2]
         net, keep = ops.sdf_net(r.sdf_network.layout(), pk)
+        col_packed = r.color_network.params_and_pack(fold_feature=(sdf_packed[0][-1], sdf_packed[1][-1]))
+        cnet, ckeep = ops.color_net(r.color_network.layout(), col_packed[2])
         for n in a.res:
             N, C = n ** 3, (n - 1) ** 3
             u = torch.empty(n, n, n, device=dev)
@@ -115,6 +121,28 @@ def main(argv=None):
             base = _stat(_host(lambda: baseline_fields(r.sdf_network, n, a.time), a.baseline_repeats))
             ub = baseline_fields(r.sdf_network, n, a.time)
             same = float((torch.from_numpy(ub) - u.cpu()).abs().max())
+            # the colour pass (one cn_point_colors call) next to the chunked module composition with the same
+            # packs, and the clean pass (host clock: it reads `changed` and the counts back)
+            rgb = torch.empty(V, 3, device=dev)
+
+            def composed(chunk=1 << 18):
+                for i in range(0, V, chunk):
+                    v = vert[i:i + chunk]
+                    pts = torch.cat([v, t.expand(v.shape[0], 1)], dim=1)
+                    _, feat, G = r.sdf_network.field(pts, want_feat="hidden", want_grad=True, packed=sdf_packed)
+                    rgb[i:i + chunk] = r.color_network.color(pts, G, ops.vertex_dirs(G), 1, feat, packed=col_packed)
+                return rgb
+
+            color = _stat(_events(lambda: ops.point_colors(net, cnet, vert, t), a.repeats))
+            color_py = _stat(_events(composed, a.repeats))
+            color_same = bool(torch.equal(ops.point_colors(net, cnet, vert, t), composed()))
+            cstats = {}
+            clean = _stat(_host(lambda: ops.mesh_clean(vert, tri, keep_largest=True, stats=cstats), a.repeats))
+            color_rows.append({
+                "res": n, "vertices": V, "triangles": T, "point_colors": color, "composition": color_py,
+                "composition_bitwise_equal": color_same, "point_colors_rows_per_s": V / (color["median_ms"] * 1e-3),
+                "mesh_clean_keep_largest": clean, "components": cstats["components"], "label_rounds": cstats["rounds"],
+            })
             count_bytes = 4 * N + N + C + 4 * N + 4 * C + 16
             emit_bytes = 4 * N + 12 * V + 12 * T
             rows.append({
@@ -126,9 +154,10 @@ def main(argv=None):
                 "speedup_fields": base["median_ms"] / grid["median_ms"],
             })
             del u, ws, vert, tri
-        del keep
+        del keep, ckeep
     res = {"library": stamp, "device": torch.cuda.get_device_name(0), "mode": "bf16x6", "time_step": a.time,
            "repeats": a.repeats, "rows": rows}
+    color_res = dict(res, rows=color_rows)
     f = lambda s: f'{s["median_ms"]:.2f} ({s["min_ms"]:.2f} .. {s["max_ms"]:.2f})'  # noqa: E731
     lines = [f"library {stamp}, {res['device']}, bf16x6, median (min .. max) ms of {a.repeats} calls "
              f"(baseline: {a.baseline_repeats})", "",
@@ -138,13 +167,23 @@ def main(argv=None):
         lines.append(f'| {w["res"]}^3 | {w["vertices"]} | {w["triangles"]} | {f(w["sdf_grid"])} | '
                      f'{w["sdf_grid_rows_per_s"] / 1e6:.1f} | {f(w["baseline_fields"])} | {w["speedup_fields"]:.2f} | '
                      f'{f(w["mesh_count"])} | {w["count_GBps"]:.0f} | {f(w["mesh_emit"])} | {w["emit_GBps"]:.0f} |')
+    lines += ["", "| res | V | T | cn_point_colors | Mrows/s | chunked composition | bitwise equal | "
+              "mesh_clean keep_largest (host clock) | components | label rounds |", "|---|---|---|---|---|---|---|---|---|---|"]
+    for w in color_rows:
+        lines.append(f'| {w["res"]}^3 | {w["vertices"]} | {w["triangles"]} | {f(w["point_colors"])} | '
+                     f'{w["point_colors_rows_per_s"] / 1e6:.1f} | {f(w["composition"])} | '
+                     f'{w["composition_bitwise_equal"]} | {f(w["mesh_clean_keep_largest"])} | {w["components"]} | '
+                     f'{w["label_rounds"]} |')
     table = "\n".join(lines)
     print(table)
     print(json.dumps(res))
+    print(json.dumps(color_res))
     if a.out:
         os.makedirs(a.out, exist_ok=True)
         with open(os.path.join(a.out, "mesh_bench.json"), "w") as fh:
             json.dump(res, fh, indent=1)
+        with open(os.path.join(a.out, "mesh_color_bench.json"), "w") as fh:
+            json.dump(color_res, fh, indent=1)
         with open(os.path.join(a.out, "mesh_bench.md"), "w") as fh:
             fh.write(table + "\n")
     return res
