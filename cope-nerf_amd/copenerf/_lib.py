@@ -182,6 +182,34 @@ class MeshCleanDesc(ctypes.Structure):
     ]
 
 
+class MeshSampleDesc(ctypes.Structure):
+    _fields_ = [
+        ("V", c_i64), ("T", c_i64), ("vertices", c_ptr), ("triangles", c_ptr), ("area", c_ptr), ("S", c_i64),
+        ("philox", c_ptr), ("points", c_ptr), ("tri", c_ptr),
+    ]
+
+
+class NnGridDesc(ctypes.Structure):
+    _fields_ = [
+        ("N", c_i64), ("points", c_ptr), ("origin", c_f32 * 3), ("cell", c_f32), ("dims", c_i32 * 3),
+        ("cell_start", c_ptr), ("sorted", c_ptr),
+    ]
+
+
+class NnQueryDesc(ctypes.Structure):
+    _fields_ = [
+        ("grid", ctypes.POINTER(NnGridDesc)), ("Q", c_i64), ("queries", c_ptr), ("query_records", c_i32),
+        ("max_dist", c_f32), ("dist", c_ptr), ("index", c_ptr),
+    ]
+
+
+class CloudStatsDesc(ctypes.Structure):
+    _fields_ = [
+        ("Q", c_i64), ("dist", c_ptr), ("points", c_ptr), ("crop_min", c_f32 * 3), ("crop_max", c_f32 * 3),
+        ("max_dist", c_f32), ("threshold", c_f32), ("out", c_ptr),
+    ]
+
+
 LPIPS_CONVS, LPIPS_TAPS = 13, 5
 
 
@@ -285,6 +313,14 @@ SIGNATURES = {
     "cn_mesh_clean_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32]),
     "cn_mesh_select": (c_i32, [ctypes.POINTER(MeshCleanDesc), c_ptr, c_i64, c_ptr]),
     "cn_mesh_compact": (c_i32, [ctypes.POINTER(MeshCleanDesc), c_ptr, c_i64, c_ptr]),
+    "cn_mesh_sample_workspace_bytes": (ctypes.c_size_t, [c_i64]),
+    "cn_mesh_area": (c_i32, [ctypes.POINTER(MeshSampleDesc), c_ptr, c_i64, c_ptr]),
+    "cn_mesh_sample": (c_i32, [ctypes.POINTER(MeshSampleDesc), c_ptr, c_i64, c_ptr]),
+    "cn_nn_grid_workspace_bytes": (ctypes.c_size_t, [c_i64, c_i64]),
+    "cn_nn_grid_build": (c_i32, [ctypes.POINTER(NnGridDesc), c_ptr, c_i64, c_ptr]),
+    "cn_nn_query": (c_i32, [ctypes.POINTER(NnQueryDesc), c_ptr]),
+    "cn_cloud_stats_workspace_bytes": (ctypes.c_size_t, [c_i64]),
+    "cn_cloud_stats": (c_i32, [ctypes.POINTER(CloudStatsDesc), c_ptr, c_i64, c_ptr]),
     "cn_refine_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32]),
     "cn_refine_warp": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
                                c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),

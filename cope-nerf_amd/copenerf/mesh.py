@@ -1,5 +1,6 @@
 """Mesh files for NeuSRenderer.extract_geometry: a binary little-endian PLY writer (the reference writes its
-meshes through trimesh, which this package does not depend on)."""
+meshes through trimesh, which this package does not depend on) and the reader the geometry metrics load
+meshes and ground-truth clouds with."""
 from __future__ import annotations
 
 import numpy as np
@@ -43,3 +44,118 @@ def write_ply(path, vertices, triangles, normals=None, colors=None):
         out.write(header.encode("ascii"))
         out.write(rows.tobytes())
         out.write(faces.tobytes())
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2",
+              "ushort": "u2", "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4",
+              "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def _ply_header(f, path):
+    """The elements of a PLY header, in file order: (format, [(name, count, [property, ...])]) with a property
+    (name, type) or (name, count type, item type) for a list."""
+    if f.readline().strip() != b"ply":
+        raise ValueError(f"read_ply: {path} is not a PLY file")
+    fmt, elements = None, []
+    while True:
+        line = f.readline()
+        if not line:
+            raise ValueError(f"read_ply: {path}: the header does not end")
+        w = line.decode("ascii", "replace").split()
+        if not w or w[0] in ("comment", "obj_info"):
+            continue
+        if w[0] == "format":
+            fmt = w[1]
+        elif w[0] == "element":
+            elements.append((w[1], int(w[2]), []))
+        elif w[0] == "property":
+            if not elements:
+                raise ValueError(f"read_ply: {path}: a property before any element")
+            try:
+                prop = (w[4], _PLY_TYPES[w[2]], _PLY_TYPES[w[3]]) if w[1] == "list" else (w[2], _PLY_TYPES[w[1]])
+            except (KeyError, IndexError):
+                raise ValueError(f"read_ply: {path}: cannot read the property line {line!r}") from None
+            elements[-1][2].append(prop)
+        elif w[0] == "end_header":
+            break
+    if fmt == "binary_big_endian":
+        raise ValueError(f"read_ply: {path} is big-endian; only ascii and binary_little_endian are read")
+    if fmt not in ("ascii", "binary_little_endian"):
+        raise ValueError(f"read_ply: {path}: format {fmt!r}")
+    return fmt, elements
+
+
+def _ply_faces(f, path, fmt, count, props, tokens):
+    """The face element as int32 [count, 3]: the first list property holds the vertex indices; every face must
+    be a triangle."""
+    lists = [p for p in props if len(p) == 3]
+    if not lists or props[0] is not lists[0] or len(lists) > 1:
+        raise ValueError(f"read_ply: {path}: faces must start with their one index list")
+    _, ctype, itype = lists[0]
+    if ctype not in ("u1", "i1", "i4", "u4", "i2", "u2") or itype not in ("i4", "u4"):
+        raise ValueError(f"read_ply: {path}: faces must be `list uchar|int int|uint`")
+    tail = [(n, "<" + t) for n, t in props[1:]]
+    if fmt == "ascii":
+        width = 4 + len(tail)
+        rows = np.array(tokens(count * width), dtype=np.float64).reshape(count, width) if count else np.zeros((0, width))
+        if count and not np.all(rows[:, 0] == 3):
+            raise ValueError(f"read_ply: {path} has a face that is not a triangle")
+        return rows[:, 1:4].astype(np.int64).astype(np.int32)
+    rec = np.dtype([("n", "<" + ctype), ("i", "<" + itype, (3,))] + tail)
+    raw = f.read(rec.itemsize * count)
+    # (a face with another count shifts the records: the counts stop reading 3, here or in a later record)
+    faces = np.frombuffer(raw[:len(raw) // rec.itemsize * rec.itemsize], dtype=rec)
+    if len(faces) != count or not np.all(faces["n"] == 3):
+        raise ValueError(f"read_ply: {path} has a face that is not a triangle")
+    return faces["i"].astype(np.int32)
+
+
+def read_ply(path):
+    """Read a PLY mesh or point cloud: (vertices float32 [V, 3], triangles int32 [T, 3] or None without a face
+    element, normals float32 [V, 3] or None, colors uint8 [V, 3] or None).  ASCII and binary little-endian
+    files; x y z (and nx ny nz) float or double; other vertex properties and other elements' scalar properties
+    are skipped; faces are `list uchar|int int|uint` and all triangles.  A big-endian file or a face that is
+    not a triangle raises a ValueError naming the file.  Reads back what write_ply writes."""
+    with open(path, "rb") as f:
+        fmt, elements = _ply_header(f, path)
+        words = iter(())
+        if fmt == "ascii":
+            words = iter(f.read().split())
+
+        def tokens(n):
+            out = [w for _, w in zip(range(n), words)]
+            if len(out) != n:
+                raise ValueError(f"read_ply: {path} ends early")
+            return out
+
+        vertices = triangles = normals = colors = None
+        for name, count, props in elements:
+            if name == "face":
+                triangles = _ply_faces(f, path, fmt, count, props, tokens)
+                continue
+            if any(len(p) == 3 for p in props):
+                raise ValueError(f"read_ply: {path}: a list property in element {name!r}")
+            if fmt == "ascii":
+                cols = np.array(tokens(count * len(props)), dtype=np.float64).reshape(count, len(props))
+                table = {p[0]: cols[:, i] for i, p in enumerate(props)}
+            else:
+                rec = np.dtype([(p[0], "<" + p[1]) for p in props])
+                raw = f.read(rec.itemsize * count)
+                if len(raw) != rec.itemsize * count:
+                    raise ValueError(f"read_ply: {path} ends early")
+                table = np.frombuffer(raw, dtype=rec)
+            if name != "vertex":
+                continue
+            have = {p[0] for p in props}
+            if not {"x", "y", "z"} <= have:
+                raise ValueError(f"read_ply: {path}: vertices without x y z")
+            vertices = np.stack([np.asarray(table[k], dtype=np.float32) for k in "xyz"], 1)
+            if {"nx", "ny", "nz"} <= have:
+                normals = np.stack([np.asarray(table[k], dtype=np.float32) for k in ("nx", "ny", "nz")], 1)
+            if {"red", "green", "blue"} <= have:
+                colors = np.stack([np.asarray(table[k]).astype(np.uint8) for k in ("red", "green", "blue")], 1)
+    if vertices is None:
+        raise ValueError(f"read_ply: {path} has no vertex element")
+    if triangles is not None and triangles.size and (triangles.min() < 0 or triangles.max() >= len(vertices)):
+        raise ValueError(f"read_ply: {path}: triangle index out of range")
+    return vertices, triangles, normals, colors

@@ -9,6 +9,9 @@
   pose metrics    align_ate_c2b_use_a2b, compute_ATE, compute_rpe, compute_pose_error (train.py:169-178,
                   utils_poses/align_traj.py, utils_poses/comp_ate.py, ATE/align_trajectory.py) in float64
                   numpy on the host: a few dozen 4 x 4 matrices, control plane;
+  geometry        nearest_distances (exact nearest neighbour between two clouds: cn_nn_grid_build /
+                  cn_nn_query) and mesh_geometry_metrics (Chamfer distance in the DTU style, precision /
+                  recall / F-score in the Tanks and Temples style) on the device; the reference has none;
   evaluate        render the test views (inference.render_image), keep the maps on the device, run the
                   above and merge the dictionaries in eval.py:264-267's order; write_results writes
                   results.txt (eval.py:268-270).
@@ -26,6 +29,7 @@ import numpy as np
 import torch
 
 import ctypes
+import math
 
 from . import _lib, ops
 
@@ -385,6 +389,137 @@ def compute_pose_error(pred_poses, gt_poses):
     ate = compute_ATE(gt_poses, aligned)
     rpe_trans, rpe_rot = compute_rpe(gt_poses, aligned)
     return aligned, rpe_trans * 100, rpe_rot * 180 / np.pi, ate
+
+
+# ---------------------------------------------------------------------------
+# geometry metrics (device)
+GEOMETRY_KEYS = ("accuracy", "completeness", "chamfer", "precision", "recall", "fscore", "n_pred", "n_gt",
+                 "n_pred_far", "n_gt_far", "area")
+NN_TARGETS_PER_CELL = 8
+# nearest_distances' default for sort_queries: the arm tools/mesh_eval_bench.py measured as faster
+# (profiles/mesh_eval_bench.json)
+SORT_QUERIES_DEFAULT = True
+
+
+def nn_cell_size(lo, hi, n, per_cell=NN_TARGETS_PER_CELL, max_cells=ops.NN_MAX_CELLS):
+    """(cell, dims) of the grid nearest_distances lays over n targets in the box lo .. hi: cubic cells that
+    hold per_cell targets on average over the box (axes of zero extent count as one cell thick), the edge
+    enlarged until the grid has at most max_cells cells.  dims covers the box: hi falls in the last cell."""
+    ext = [max(float(h) - float(l), 0.0) for l, h in zip(lo, hi)]
+    live = [e for e in ext if e > 0.0]
+    if not live:
+        return 1.0, (1, 1, 1)
+    cell = (math.prod(live) * per_cell / max(int(n), 1)) ** (1.0 / len(live))
+    cell = max(cell, max(live) * 2.0 ** -20, 1e-30)
+    while True:
+        dims = tuple(int(e / cell) + 1 for e in ext)
+        cells = dims[0] * dims[1] * dims[2]
+        if cells <= max_cells:
+            return cell, dims
+        cell *= max((cells / max_cells) ** (1.0 / len(live)), 1.0 + 2.0 ** -10)
+
+
+def nearest_distances(queries, targets, max_dist=math.inf, cell=None, sort_queries=None):
+    """(dist fp32 [Q], index int32 [Q]): for every query the distance to and the index of its nearest target,
+    exact (a uniform grid over the targets searched in Chebyshev shells: cn_nn_grid_build / cn_nn_query), ties
+    to the smaller index; (max_dist, -1) where no target is nearer than max_dist.  queries [Q, 3] and targets
+    [N, 3] are fp32 device tensors.  cell: the grid's cell edge, by default nn_cell_size's (about 8 targets per
+    cell); the grid covers the targets' bounding box (one 24-byte read-back).  sort_queries (default
+    SORT_QUERIES_DEFAULT) bins the queries through the same counting sort on the targets' grid first, so that a
+    wave's lanes walk neighbouring cells; the outputs are bitwise the same either way."""
+    ops._need_cloud("nearest_distances", queries, "queries")
+    ops._need_cloud("nearest_distances", targets, "targets")
+    if queries.device != targets.device:
+        raise RuntimeError("nearest_distances: queries and targets on different devices")
+    if sort_queries is None:
+        sort_queries = SORT_QUERIES_DEFAULT
+    N, Q = targets.shape[0], queries.shape[0]
+    if N == 0:
+        return (torch.full((Q,), float(max_dist), dtype=torch.float32, device=queries.device),
+                torch.full((Q,), -1, dtype=torch.int32, device=queries.device))
+    box = torch.stack([targets.amin(0), targets.amax(0)]).tolist()
+    if not all(math.isfinite(x) for x in box[0] + box[1]):
+        raise ValueError("nearest_distances: targets must be finite")
+    if cell is None:
+        cell, dims = nn_cell_size(box[0], box[1], N)
+    else:
+        cell = float(cell)
+        if not cell > 0.0:
+            raise ValueError(f"nearest_distances: cell {cell}")
+        dims = tuple(int((h - l) / cell) + 1 for l, h in zip(*box))
+        if dims[0] * dims[1] * dims[2] > ops.NN_MAX_CELLS:
+            raise ValueError(f"nearest_distances: cell {cell} gives {dims} cells, more than 2^26")
+    grid = ops.nn_grid(targets, box[0], cell, dims)
+    if sort_queries and Q > 0:
+        binned = ops.nn_grid(queries, box[0], cell, dims)
+        return ops.nn_query(grid, binned.sorted, max_dist, records=True)
+    return ops.nn_query(grid, queries, max_dist)
+
+
+def _cloud_side(queries, targets, threshold, max_dist, crop_min, crop_max):
+    dist, _ = nearest_distances(queries, targets, max_dist)
+    return ops.cloud_stats(dist, threshold, max_dist, queries if crop_min is not None else None, crop_min, crop_max)
+
+
+def geometry_from_stats(pred, gt, area):
+    """The metric dict from the two cn_cloud_stats results (4 numbers each: inside the crop, of those within
+    max_dist, the sum of their distances, of those below the threshold), mesh samples first."""
+    (np_, npn, sp, hp), (ng, ngn, sg, hg) = pred, gt
+    acc = sp / npn if npn else float("nan")
+    comp = sg / ngn if ngn else float("nan")
+    P = hp / np_ if np_ else 0.0
+    R = hg / ng if ng else 0.0
+    return {"accuracy": acc, "completeness": comp, "chamfer": 0.5 * (acc + comp), "precision": P, "recall": R,
+            "fscore": 2.0 * P * R / (P + R) if P + R > 0 else 0.0, "n_pred": int(np_), "n_gt": int(ng),
+            "n_pred_far": int(np_ - npn), "n_gt_far": int(ng - ngn), "area": area}
+
+
+def mesh_geometry_metrics(vertices, triangles, gt_points, *, threshold, max_dist=math.inf, n_samples=None,
+                          density=None, seed=0, transform=None, crop_min=None, crop_max=None):
+    """Geometry metrics of a triangle mesh against a ground-truth cloud, all on the device.  vertices fp32
+    [V, 3], triangles int32 [T, 3] (NeuSRenderer.extract_geometry's output as it is) and gt_points fp32 [N, 3]
+    are device tensors.  The mesh is sampled uniformly by area (cn_mesh_area / cn_mesh_sample, Philox seed
+    `seed`) with n_samples points or density points per unit area -- exactly one of the two -- after
+    `transform`, a 4 x 4 similarity applied to the vertices (e.g. align_ate_c2b_use_a2b's Sim(3)).  Points
+    outside the axis-aligned box crop_min .. crop_max (both or neither) are left out on both sides.
+      accuracy      mean distance from the mesh samples to gt_points, over the samples nearer than max_dist;
+      completeness  the same from gt_points to the mesh samples;  chamfer = (accuracy + completeness) / 2;
+      precision / recall  the share of mesh samples / ground-truth points with distance < threshold (a point
+                    farther than max_dist is a miss);  fscore = 2 P R / (P + R), 0 when P + R = 0;
+      n_pred, n_gt, n_pred_far, n_gt_far  the points counted on either side and those beyond max_dist;  area.
+    The samples and the distances stay on the device; what comes back is the area (8 bytes), the two
+    bounding boxes and two double [4] statistics."""
+    if (n_samples is None) == (density is None):
+        raise ValueError("mesh_geometry_metrics: exactly one of n_samples and density")
+    if (crop_min is None) != (crop_max is None):
+        raise ValueError("mesh_geometry_metrics: crop_min and crop_max together")
+    if not threshold > 0 or not max_dist > 0:
+        raise ValueError(f"mesh_geometry_metrics: threshold {threshold}, max_dist {max_dist}")
+    ops._need_cloud("mesh_geometry_metrics", vertices, "vertices")
+    ops._need_cloud("mesh_geometry_metrics", triangles, "triangles", dtype=torch.int32)
+    ops._need_cloud("mesh_geometry_metrics", gt_points, "gt_points")
+    dev = vertices.device
+    if transform is not None:
+        M = torch.as_tensor(np.asarray(transform.detach().cpu() if torch.is_tensor(transform) else transform,
+                                       dtype=np.float64), dtype=torch.float32).to(dev)
+        if M.shape != (4, 4):
+            raise ValueError(f"mesh_geometry_metrics: transform must be 4 x 4, got {tuple(M.shape)}")
+        vertices = (vertices @ M[:3, :3].T + M[:3, 3]).contiguous()
+    if triangles.shape[0] == 0:
+        raise ValueError("mesh_geometry_metrics: a mesh without triangles")
+    handle, area_dev = ops.mesh_area(vertices, triangles)
+    area = float(area_dev.item())
+    if not area > 0.0:
+        raise ValueError("mesh_geometry_metrics: a mesh of zero area")
+    S = int(n_samples) if n_samples is not None else int(math.ceil(float(density) * area))
+    if S < 1 or S >= 2 ** 31:
+        raise ValueError(f"mesh_geometry_metrics: {S} samples")
+    philox = torch.tensor([int(seed), 0], dtype=torch.uint64, device=dev)
+    samples, _ = ops.mesh_sample(handle, S, philox)
+    pred = _cloud_side(samples, gt_points, threshold, max_dist, crop_min, crop_max)
+    gt = _cloud_side(gt_points, samples, threshold, max_dist, crop_min, crop_max)
+    both = torch.stack([pred, gt]).tolist()
+    return geometry_from_stats(both[0], both[1], area)
 
 
 # ---------------------------------------------------------------------------

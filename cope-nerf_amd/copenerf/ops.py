@@ -1297,6 +1297,137 @@ def mesh_clean(vertices, triangles, keep_largest=False, min_triangles=0, stats=N
 
 
 # ---------------------------------------------------------------------------
+# Mesh geometry metrics (additive to ABI v22): cn_mesh_eval.hip
+NN_MAX_CELLS = 1 << 26
+
+
+def _need_cloud(fn, t, name, cols=3, dtype=torch.float32):
+    _need(t, name, ndim=0)
+    if t.dtype != dtype or t.dim() != 2 or t.shape[1] != cols or not t.is_contiguous():
+        raise RuntimeError(f"{fn}: {name} must be a contiguous {dtype} [n, {cols}] device tensor (got {t.dtype}, "
+                           f"shape {tuple(t.shape)})")
+
+
+def _workspace(nbytes, dev):
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+
+
+def mesh_area(vertices, triangles):
+    """The first phase of the surface sampler -- cn_mesh_area: (handle, area) with area a device double [1], the
+    mesh's area (the sum of the triangle areas in double from the fp32 vertices), and handle what mesh_sample
+    takes: the descriptor, the workspace that keeps the areas' inclusive scan, and the mesh's tensors.  Reading
+    area (one host read) lets the caller fix the number of samples by density."""
+    _need_cloud("mesh_area", vertices, "vertices")
+    _need_cloud("mesh_area", triangles, "triangles", dtype=torch.int32)
+    dev = vertices.device
+    d = _lib.MeshSampleDesc()
+    d.V, d.T = vertices.shape[0], triangles.shape[0]
+    d.vertices, d.triangles = _ptr(vertices) if d.V else None, _ptr(triangles) if d.T else None
+    area = torch.empty(1, dtype=torch.float64, device=dev)
+    d.area = _ptr(area)
+    lib = _lib.load()
+    ws = _workspace(lib.cn_mesh_sample_workspace_bytes(d.T), dev)
+    _lib.check(lib.cn_mesh_area(ctypes.byref(d), _ptr(ws), ws.numel(), _stream()), "cn_mesh_area")
+    return (d, ws, (vertices, triangles)), area
+
+
+def mesh_sample(handle, S, seed_offset, want_tri=False):
+    """S points uniformly by area on the mesh of mesh_area's handle -- cn_mesh_sample: (points fp32 [S, 3],
+    tri int32 [S] or None).  seed_offset: a device uint64 [2] = (seed, offset); sample i takes elements
+    4 i .. 4 i + 2 of uniform_philox's stream for it."""
+    d, ws, _ = handle
+    _check_philox(seed_offset)
+    dev = ws.device
+    S = int(S)
+    points = torch.empty(max(S, 0), 3, dtype=torch.float32, device=dev)
+    tri = torch.empty(max(S, 0), dtype=torch.int32, device=dev) if want_tri else None
+    d.S, d.philox = S, _ptr(seed_offset)
+    d.points, d.tri = (_ptr(points), _ptr(tri)) if S > 0 else (None, None)
+    _lib.call("cn_mesh_sample", ctypes.byref(d), _ptr(ws), ws.numel(), _stream())
+    return points, tri
+
+
+class NnGrid:
+    """A built point grid (nn_grid): the descriptor and the device buffers it points into."""
+
+    def __init__(self, d, points, cell_start, sorted_):
+        self.desc, self.points, self.cell_start, self.sorted = d, points, cell_start, sorted_
+        self.origin, self.cell, self.dims = tuple(d.origin), float(d.cell), tuple(d.dims)
+
+
+def nn_grid(points, origin, cell, dims):
+    """cn_nn_grid_build: the uniform grid of dims cubic cells of edge `cell` from `origin` over points fp32
+    [N, 3]: cell_start int32 [ncells + 1] and the points sorted by cell as 16-byte records (x, y, z, original
+    index).  Points outside the grid go to the nearest boundary cell."""
+    _need_cloud("nn_grid", points, "points")
+    dev = points.device
+    dims = tuple(int(x) for x in dims)
+    ncells = dims[0] * dims[1] * dims[2]
+    if min(dims) < 1 or ncells > NN_MAX_CELLS:
+        raise RuntimeError(f"nn_grid: dims {dims} (each at least 1, at most 2^26 cells)")
+    d = _lib.NnGridDesc()
+    d.N = points.shape[0]
+    d.points = _ptr(points) if d.N else None
+    d.origin, d.cell, d.dims = (_lib.c_f32 * 3)(*[float(x) for x in origin]), float(cell), (_lib.c_i32 * 3)(*dims)
+    cell_start = torch.empty(ncells + 1, dtype=torch.int32, device=dev)
+    sorted_ = torch.empty(max(d.N, 1), 4, dtype=torch.float32, device=dev)
+    d.cell_start, d.sorted = _ptr(cell_start), _ptr(sorted_)
+    lib = _lib.load()
+    ws = _workspace(lib.cn_nn_grid_workspace_bytes(d.N, ncells), dev)
+    _lib.check(lib.cn_nn_grid_build(ctypes.byref(d), _ptr(ws), ws.numel(), _stream()), "cn_nn_grid_build")
+    return NnGrid(d, points, cell_start, sorted_)
+
+
+def nn_query(grid, queries, max_dist=math.inf, want_index=True, records=False):
+    """cn_nn_query: (dist fp32 [Q], index int32 [Q] or None), the distance to and the original index of the
+    nearest point of `grid` for every query, exact, ties to the smaller index; (max_dist, -1) where no point is
+    nearer than max_dist.  queries: fp32 [Q, 3], or with records=True the `sorted` records [Q, 4] of an nn_grid
+    over the queries -- then every output lands at its query's original position."""
+    _need_cloud("nn_query", queries, "queries", cols=4 if records else 3)
+    if queries.device != grid.sorted.device:
+        raise RuntimeError("nn_query: queries and grid on different devices")
+    dev = queries.device
+    Q = queries.shape[0]
+    dist = torch.empty(Q, dtype=torch.float32, device=dev)
+    index = torch.empty(Q, dtype=torch.int32, device=dev) if want_index else None
+    d = _lib.NnQueryDesc()
+    d.grid = ctypes.pointer(grid.desc)
+    d.Q, d.queries, d.query_records, d.max_dist = Q, _ptr(queries) if Q else None, int(bool(records)), float(max_dist)
+    d.dist, d.index = (_ptr(dist), _ptr(index)) if Q else (None, None)
+    _lib.call("cn_nn_query", ctypes.byref(d), _stream())
+    return dist, index
+
+
+def cloud_stats(dist, threshold, max_dist=math.inf, points=None, crop_min=None, crop_max=None):
+    """cn_cloud_stats: a device double [4] = (points inside the crop box, those with dist < max_dist, the sum of
+    their distances, those of them with dist < threshold) over dist fp32 [Q]; points fp32 [Q, 3] with crop_min /
+    crop_max (3 floats each) restrict it to a box, without them every point counts."""
+    _need(dist, "dist", ndim=0)
+    if dist.dtype != torch.float32 or dist.dim() != 1 or not dist.is_contiguous():
+        raise RuntimeError("cloud_stats: dist must be a contiguous fp32 [Q] device tensor")
+    dev = dist.device
+    d = _lib.CloudStatsDesc()
+    d.Q = dist.shape[0]
+    d.dist = _ptr(dist) if d.Q else None
+    if (crop_min is None) != (crop_max is None) or (crop_min is not None and points is None):
+        raise RuntimeError("cloud_stats: a crop box needs crop_min, crop_max and points")
+    if crop_min is not None:
+        _need_cloud("cloud_stats", points, "points")
+        if points.shape[0] != d.Q or points.device != dev:
+            raise RuntimeError(f"cloud_stats: points {tuple(points.shape)} for {d.Q} distances")
+        d.points = _ptr(points) if d.Q else None
+        d.crop_min = (_lib.c_f32 * 3)(*[float(x) for x in crop_min])
+        d.crop_max = (_lib.c_f32 * 3)(*[float(x) for x in crop_max])
+    d.max_dist, d.threshold = float(max_dist), float(threshold)
+    out = torch.empty(4, dtype=torch.float64, device=dev)
+    d.out = _ptr(out)
+    lib = _lib.load()
+    ws = _workspace(lib.cn_cloud_stats_workspace_bytes(d.Q), dev)
+    _lib.check(lib.cn_cloud_stats(ctypes.byref(d), _ptr(ws), ws.numel(), _stream()), "cn_cloud_stats")
+    return out
+
+
+# ---------------------------------------------------------------------------
 # Pose refinement (ABI v17)
 class _RefineWarp(torch.autograd.Function):
     """cn_refine_warp: the forward launches the fused pass and keeps dpose = d sums[:, 0] / d pose; the

@@ -71,6 +71,59 @@ __device__ __forceinline__ float softplus_grad_ref(float x, float beta, float th
 
 __host__ __device__ __forceinline__ int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; the Random123
+// constants): ten rounds of two 32x32 -> 64-bit multiplies, the key bumped by the Weyl constants between rounds.
+// Shared by cn_uniform_philox (cn_render.hip) and the surface sampler (cn_mesh_eval.hip).
+__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+    for (int r = 0; r < 10; ++r) {
+        if (r) {
+            k0 += 0x9E3779B9u;
+            k1 += 0xBB67AE85u;
+        }
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
+        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+        c[0] = n0;
+        c[1] = (uint32_t)p1;
+        c[2] = n2;
+        c[3] = (uint32_t)p0;
+    }
+}
+
+// The integer scans of the mesher (cn_mesh.hip) and of the point grid (cn_mesh_eval.hip): 256 threads of
+// 4 elements, reduce per 1024-element tile, one block scans the tile totals, a third launch adds back.
+constexpr int kScanThreads = 256;
+constexpr int kScanItems = 4;
+constexpr int kScanTile = kScanThreads * kScanItems;  // elements per block of the reduce / add-back launches
+
+__device__ __forceinline__ int wave_incl_scan_add_i(int x, int lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int y = __shfl_up(x, off, 64);
+        if (lane >= off) x += y;
+    }
+    return x;
+}
+
+// Exclusive scan of one value per thread over the block's 256 threads; *total = the block's sum.
+__device__ __forceinline__ int block_excl_scan(int x, int* total) {
+    __shared__ int wsum[kScanThreads / kWave];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int incl = wave_incl_scan_add_i(x, lane);
+    __syncthreads();  // (a previous round's readers are done)
+    if (lane == 63) wsum[w] = incl;
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int i = 0; i < kScanThreads / kWave; ++i) {
+        if (i < w) before += wsum[i];
+        all += wsum[i];
+    }
+    *total = all;
+    return before + incl - x;
+}
+
 // grid_sample's border clip of an unnormalised coordinate (GridSampler.h clip_coordinates_set_grad):
 // the clamped coordinate, *mult = 0 where it was clamped (the borders count as clamped).  Shared by the
 // two bilinear warps (cn_refine.hip, cn_flow_rgb.hip).

@@ -21,38 +21,9 @@
 namespace cn {
 namespace {
 
-constexpr int kScanThreads = 256;
-constexpr int kScanItems = 4;
-constexpr int kScanTile = kScanThreads * kScanItems;  // elements per block of the reduce / add-back launches
-
 __constant__ TetTable kTet = make_tet_table();
 
-__device__ __forceinline__ int wave_incl_scan_add_i(int x, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int y = __shfl_up(x, off, 64);
-        if (lane >= off) x += y;
-    }
-    return x;
-}
-
-// Exclusive scan of one value per thread over the block's 256 threads; *total = the block's sum.
-__device__ __forceinline__ int block_excl_scan(int x, int* total) {
-    __shared__ int wsum[kScanThreads / kWave];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int incl = wave_incl_scan_add_i(x, lane);
-    __syncthreads();  // (a previous round's readers are done)
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int i = 0; i < kScanThreads / kWave; ++i) {
-        if (i < w) before += wsum[i];
-        all += wsum[i];
-    }
-    *total = all;
-    return before + incl - x;
-}
+// (the scans' block_excl_scan and tile constants: cn_common.h)
 
 // torch.linspace(lo, hi, n)[i] on fp32 (RangeFactoriesKernel.cpp): from lo below the middle, from hi above
 __device__ __forceinline__ float linspace_at(float lo, float hi, int n, int i) {

@@ -75,25 +75,7 @@ __global__ void coarse_z_kernel(int R, int n, const float* __restrict__ near, co
     z[idx] = lower + (upper - lower) * t_rand[idx];
 }
 
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; the Random123
-// constants): ten rounds of two 32x32 -> 64-bit multiplies, the key bumped by the Weyl constants between rounds.
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-    for (int r = 0; r < 10; ++r) {
-        if (r) {
-            k0 += 0x9E3779B9u;
-            k1 += 0xBB67AE85u;
-        }
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-        c[0] = n0;
-        c[1] = (uint32_t)p1;
-        c[2] = n2;
-        c[3] = (uint32_t)p0;
-    }
-}
-
+// (philox4x32_10: cn_common.h)
 // out[i] = the 24 high bits of word i % 4 of Philox4x32-10(counter (i / 4, offset), key seed) x 2^-24, in [0, 1);
 // seed and offset are read on the device (so = [seed, offset]: a captured launch replays with the current values)
 __global__ void __launch_bounds__(256) uniform_philox_kernel(int64_t n, const uint64_t* __restrict__ so,

@@ -951,6 +951,113 @@ int cn_mesh_select(const cn_mesh_clean_desc* d, void* workspace, int64_t workspa
 int cn_mesh_compact(const cn_mesh_clean_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * Mesh geometry metrics (additive to ABI v22): Chamfer distance and precision / recall /
+ * F-score between a mesh and a point cloud without leaving the device.  The reference has no
+ * geometry metric; the yardstick is float64 brute force.  Sizes are int64 so that a size at
+ * or above 2^31 is refused (CN_ERR_SHAPE) instead of wrapping: V, T, S, N, Q < 2^31, and a
+ * grid has at most 2^26 cells.  All checks run before any launch.
+ *
+ * cn_mesh_area / cn_mesh_sample: S points uniformly by area on vertices [V][3] fp32 /
+ * triangles [T][3] int32.  cn_mesh_area computes every triangle's area in double from the
+ * fp32 corners (0 for a corner index outside [0, V) or a non-finite area), leaves their
+ * inclusive scan cdf [T] (double) in the workspace and writes area (DEVICE double [1]) =
+ * cdf[T - 1] (0 when T = 0): the caller may read it -- one host read -- before fixing S.
+ * The scan is a nest of sequential sums (4 triangles per thread, 64 threads per wave in
+ * lane order, 4 waves per 1024-triangle tile, the tiles in order by one wave): bitwise
+ * repeatable, never falling, and a zero-area triangle repeats its predecessor exactly.
+ * cn_mesh_sample, with the same descriptor and workspace, draws sample i from
+ * (u0, u1, u2) = elements 4 i, 4 i + 1, 4 i + 2 of cn_uniform_philox's stream for philox
+ * (DEVICE uint64 [2] = (seed, offset)), i.e. words 0, 1, 2 of Philox4x32-10(counter
+ * (i, offset), key seed), word 3 unused (the caller advances offset by S per draw of S
+ * samples): tri[i] = the first t with cdf[t] > u0 area in double, by binary search (never
+ * a zero-area triangle), points[i] = ((1 - r) a + r (1 - u2) b) + r u2 c in fp32 with
+ * r = sqrtf(u1) and (a, b, c) the triangle's corners.  tri may be NULL.  With area = 0 the
+ * points are zeros and tri is -1.  S > 0 with T = 0 is CN_ERR_SHAPE.
+ * Workspace (256-byte aligned): 8 T (the cdf) + 8 max(1, ceil(T / 1024)) (the tile totals),
+ * each rounded up to 256 bytes.
+ * ------------------------------------------------------------------------ */
+typedef struct cn_mesh_sample_desc {
+    int64_t V, T;
+    const float* vertices;              /* [V][3] */
+    const int32_t* triangles;           /* [T][3] */
+    double* area;                       /* device [1] -- written by cn_mesh_area, read by cn_mesh_sample */
+    int64_t S;                          /* cn_mesh_sample only, as are the fields below */
+    const uint64_t* philox;             /* device [2] = (seed, offset) */
+    float* points;                      /* [S][3] */
+    int32_t* tri;                       /* [S], or NULL */
+} cn_mesh_sample_desc;
+size_t cn_mesh_sample_workspace_bytes(int64_t T);
+int cn_mesh_area(const cn_mesh_sample_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+int cn_mesh_sample(const cn_mesh_sample_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+
+/* cn_nn_grid_build: a uniform grid of dims[0] x dims[1] x dims[2] cubic cells of edge `cell`
+ * from `origin` (HOST values) over points [N][3].  The cell of a point is, per axis,
+ * floor((p - origin) / cell) clamped into the grid (a point outside goes to the nearest
+ * boundary cell, a NaN to cell 0); the cell id is (ix dims[1] + iy) dims[2] + iz.  An
+ * integer-atomic histogram and an exclusive int32 scan give cell_start [ncells + 1]
+ * (cell_start[ncells] = N); the points are scattered into sorted [N][4]: 16-byte records
+ * (x, y, z, the original index as int32 bits), cell c's at [cell_start[c],
+ * cell_start[c + 1]).  The order inside a cell is the atomics'; nothing below depends on it.
+ * Workspace (256-byte aligned): 4 N (cell ids) + 4 ncells (counts) + 4 ceil(ncells / 1024)
+ * (the scan's tile totals), each rounded up to 256 bytes.
+ *
+ * cn_nn_query: for each of Q queries the exact nearest point of a built grid, one lane per
+ * query: dist [Q] and, unless NULL, index [Q] (the original index; the smaller one where
+ * squared distances tie).  d^2 = ((dx dx + dy dy) + dz dz) and dist = sqrtf(d^2) in fp32.
+ * Cells are visited in Chebyshev shells around the query's (clamped) cell until no unvisited
+ * cell can hold a nearer point (the bound holds for queries and points outside the grid:
+ * csrc/cn_mesh_eval.hip), until the bound reaches max_dist, or until the shell has left the
+ * grid on every side; at most max(dims) shells.  A query with no point at a distance below
+ * max_dist gets dist = max_dist, index = -1; max_dist = +inf searches everywhere.
+ * query_records = 0: queries [Q][3] floats, outputs in query order.  query_records = 1:
+ * queries are the `sorted` records [Q][4] of a cn_nn_grid_build over the queries (16-byte
+ * aligned), and every output goes to its record's original index -- binning the queries
+ * through the points' grid keeps a wave's lanes in neighbouring cells; the outputs are
+ * bitwise the same either way.  No workspace. */
+typedef struct cn_nn_grid_desc {
+    int64_t N;
+    const float* points;                /* [N][3] -- cn_nn_grid_build only */
+    float origin[3];
+    float cell;
+    int32_t dims[3];
+    int32_t* cell_start;                /* [ncells + 1] */
+    float* sorted;                      /* [N][4], 16-byte aligned */
+} cn_nn_grid_desc;
+size_t cn_nn_grid_workspace_bytes(int64_t N, int64_t ncells);
+int cn_nn_grid_build(const cn_nn_grid_desc* g, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+typedef struct cn_nn_query_desc {
+    const cn_nn_grid_desc* grid;        /* HOST: a grid cn_nn_grid_build has filled */
+    int64_t Q;
+    const float* queries;               /* [Q][3], or [Q][4] records */
+    int32_t query_records;
+    float max_dist;                     /* >= 0, +inf allowed */
+    float* dist;                        /* [Q] */
+    int32_t* index;                     /* [Q], or NULL */
+} cn_nn_query_desc;
+int cn_nn_query(const cn_nn_query_desc* d, cn_stream_t stream);
+
+/* cn_cloud_stats: out (DEVICE double [4]) over dist [Q] (cn_nn_query's, with the same
+ * max_dist) = (0) the points inside the crop box crop_min <= p <= crop_max (HOST values; all
+ * Q when points is NULL), (1) those of them with dist < max_dist, (2) the sum of the
+ * distances of (1), (3) those of (1) with dist < threshold.  The counts are exact; the sum
+ * is a fixed-order double reduction (thread t of block b adds elements b 256 + t + j 256
+ * blocks for j = 0, 1, ..., a fixed tree per block, one block over the block partials),
+ * bitwise repeatable.  blocks = min(1024, max(1, ceil(Q / 1024))).
+ * Workspace (256-byte aligned): 32 blocks, rounded up to 256 bytes. */
+typedef struct cn_cloud_stats_desc {
+    int64_t Q;
+    const float* dist;                  /* [Q] */
+    const float* points;                /* [Q][3], or NULL: no crop */
+    float crop_min[3];
+    float crop_max[3];
+    float max_dist;
+    float threshold;
+    double* out;                        /* device [4] */
+} cn_cloud_stats_desc;
+size_t cn_cloud_stats_workspace_bytes(int64_t Q);
+int cn_cloud_stats(const cn_cloud_stats_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * Pose refinement (ABI v17): compute_loss_and_warp_image
  * (utils_poses/pose_refinement.py:34-61) for J (target, source) jobs over one image
  * stack, with the pose gradient in the same pass -- the per-batch work of
