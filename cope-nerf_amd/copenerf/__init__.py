@@ -12,7 +12,7 @@ from .rays import PoseRetriever  # noqa: F401
 from .motion import MotionNetwork  # noqa: F401
 from .trainer import Trainer  # noqa: F401
 from .checkpoints import CheckpointIO  # noqa: F401
-from .mesh import write_ply  # noqa: F401
+from .mesh import camera_projection, cull_mesh, render_mesh_depth, write_ply  # noqa: F401
 from .pose_refine import refine_poses  # noqa: F401
 from .metrics import compute_pose_error, evaluate  # noqa: F401
 from .visualize import render_train_views, render_visdata  # noqa: F401
@@ -21,4 +21,4 @@ from . import _lib  # noqa: F401
 __all__ = ["NeuSRenderer", "SDFNetwork", "RenderingNetwork", "SingleVarianceNetwork", "NeRF",
            "EdgePreservingSmoothnessLoss", "SmoothnessLoss", "PoseRetriever", "MotionNetwork", "Trainer",
            "CheckpointIO", "write_ply", "refine_poses", "evaluate", "compute_pose_error",
-           "render_visdata", "render_train_views"]
+           "render_visdata", "render_train_views", "camera_projection", "render_mesh_depth", "cull_mesh"]

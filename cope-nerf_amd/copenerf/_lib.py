@@ -210,6 +210,21 @@ class CloudStatsDesc(ctypes.Structure):
     ]
 
 
+class MeshRasterDesc(ctypes.Structure):
+    _fields_ = [
+        ("V", c_i64), ("T", c_i64), ("vertices", c_ptr), ("triangles", c_ptr), ("N", c_i32), ("h", c_i32), ("w", c_i32),
+        ("view_batch", c_i32), ("proj", c_ptr), ("near", c_f32), ("pixel_budget", c_i32), ("depth", c_ptr),
+        ("tri", c_ptr), ("stats", c_ptr),
+    ]
+
+
+class MeshVisibilityDesc(ctypes.Structure):
+    _fields_ = [
+        ("Q", c_i64), ("points", c_ptr), ("N", c_i32), ("h", c_i32), ("w", c_i32), ("near", c_f32), ("proj", c_ptr),
+        ("depth", c_ptr), ("tol_abs", c_f32), ("tol_rel", c_f32), ("count", c_ptr),
+    ]
+
+
 LPIPS_CONVS, LPIPS_TAPS = 13, 5
 
 
@@ -321,7 +336,11 @@ SIGNATURES = {
     "cn_nn_query": (c_i32, [ctypes.POINTER(NnQueryDesc), c_ptr]),
     "cn_cloud_stats_workspace_bytes": (ctypes.c_size_t, [c_i64]),
     "cn_cloud_stats": (c_i32, [ctypes.POINTER(CloudStatsDesc), c_ptr, c_i64, c_ptr]),
-    "cn_refine_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32]),
+    "cn_mesh_select_mask": (c_i32, [ctypes.POINTER(MeshCleanDesc), c_ptr, c_ptr, c_i64, c_ptr]),
+    "cn_mesh_raster_workspace_bytes": (ctypes.c_size_t, [c_i64, c_i64, c_i32, c_i32, c_i32, c_i32]),
+    "cn_mesh_raster": (c_i32, [ctypes.POINTER(MeshRasterDesc), c_ptr, c_i64, c_ptr]),
+    "cn_mesh_visibility": (c_i32, [ctypes.POINTER(MeshVisibilityDesc), c_ptr]),
+    "cn_refine_workspace_bytes":(ctypes.c_size_t, [c_i32, c_i32, c_i32]),
     "cn_refine_warp": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
                                c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
     "cn_image_metrics_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32, c_i32]),

@@ -1,6 +1,8 @@
 """Mesh files for NeuSRenderer.extract_geometry: a binary little-endian PLY writer (the reference writes its
 meshes through trimesh, which this package does not depend on) and the reader the geometry metrics load
-meshes and ground-truth clouds with."""
+meshes and ground-truth clouds with; and what turns a mesh back into per-view depth: camera_projection (the
+project's camera convention as one 3 x 4 matrix), render_mesh_depth and cull_mesh (the view-based cull of the
+ScanNet / DTU / Tanks-and-Temples protocols) over ops.mesh_raster / mesh_visibility / mesh_cull."""
 from __future__ import annotations
 
 import numpy as np
@@ -159,3 +161,81 @@ def read_ply(path):
     if triangles is not None and triangles.size and (triangles.min() < 0 or triangles.max() >= len(vertices)):
         raise ValueError(f"read_ply: {path}: triangle index out of range")
     return vertices, triangles, normals, colors
+
+
+# ---------------------------------------------------------------------------
+# depth rendering and view-based culling of a mesh (ops.mesh_raster / mesh_visibility / mesh_cull)
+CULL_TOL_ABS, CULL_TOL_REL = 0.0, 0.01
+
+
+def _mat4(m, name):
+    if hasattr(m, "detach"):
+        m = m.detach().cpu().numpy()
+    m = np.asarray(m, dtype=np.float64)
+    if m.shape != (4, 4):
+        raise ValueError(f"{name} must be 4 x 4, got {m.shape}")
+    return m
+
+
+def camera_projection(camera_mat, world_mat, scale_mat, resolution, transform=None):
+    """The fp32 [3, 4] projection P of a view, composed in float64: the inverse of rays.world_rays over
+    inference.arange_pixels' grid.  With (a, b, c) = P [X, 1] the point X is seen at pixel (a / c, b / c) of the
+    (h, w) = resolution image render_image renders (pixel centres at integers, x along the width), and c is the
+    depth d with X = o + d v for world_rays' un-normalised ray v through that pixel -- render_image's "depth";
+    c > 0 in front of the camera.  scale_mat may be None (identity).  transform: an optional 4 x 4 similarity S
+    applied to the geometry (as mesh_geometry_metrics' transform): P S^-1, so that the cameras of the model's
+    frame look at geometry in the transformed frame, depths staying in the model's units.  The three matrices
+    must be affine (last row 0 0 0 1), as world_rays assumes."""
+    h, w = (int(x) for x in resolution)
+    if h < 2 or w < 2:
+        raise ValueError(f"camera_projection: resolution {resolution}")
+    M = _mat4(camera_mat, "camera_mat") @ _mat4(world_mat, "world_mat")
+    if scale_mat is not None:
+        M = M @ _mat4(scale_mat, "scale_mat")
+    if not np.allclose(M[3], (0.0, 0.0, 0.0, 1.0), rtol=0.0, atol=1e-9 * max(1.0, float(np.abs(M).max()))):
+        raise ValueError("camera_projection: the camera, world and scale matrices must be affine (last row 0 0 0 1)")
+    # M [X, 1] = (d xn, d yn, d, 1) with xn = 2 x / (w - 1) - 1, yn = 2 y / (h - 1) - 1
+    P = np.stack([0.5 * (w - 1) * (M[0] + M[2]), 0.5 * (h - 1) * (M[1] + M[2]), M[2]])
+    if transform is not None:
+        P = P @ np.linalg.inv(_mat4(transform, "transform"))
+    return P.astype(np.float32)
+
+
+def view_projections(views, resolution, transform=None, device=None):
+    """camera_projection of every view -- dicts with "camera_mat", "world_mat" and optionally "scale_mat", as
+    metrics.evaluate takes them -- as one fp32 [N, 3, 4] tensor on `device`."""
+    import torch
+    P = np.stack([camera_projection(v["camera_mat"], v["world_mat"], v.get("scale_mat"), resolution, transform)
+                  for v in views]) if len(views) else np.zeros((0, 3, 4), np.float32)
+    return torch.from_numpy(P).to(device)
+
+
+def render_mesh_depth(vertices, triangles, views, resolution, transform=None, near=None, stats=None):
+    """The depth of a mesh from every view, on the device: {"depth": fp32 [N, h, w] (+inf where the view sees no
+    triangle), "tri": int32 [N, h, w] (the triangle seen, -1 where none)} for vertices fp32 [V, 3] / triangles
+    int32 [T, 3] device tensors -- ops.mesh_raster under view_projections(views, resolution, transform).  The depth
+    is in render_image's convention, so metrics.depth_metrics scores it against sensor depth as it scores a
+    rendered one."""
+    from . import ops
+    h, w = (int(x) for x in resolution)
+    proj = view_projections(views, (h, w), transform, vertices.device)
+    depth, tri = ops.mesh_raster(vertices, triangles, proj, h, w, near=ops.MESH_NEAR if near is None else near, stats=stats)
+    return {"depth": depth, "tri": tri}
+
+
+def cull_mesh(vertices, triangles, views, resolution, min_views=1, tol_abs=CULL_TOL_ABS, tol_rel=CULL_TOL_REL,
+              transform=None, near=None):
+    """The mesh cut down to what the cameras saw, as the ScanNet / DTU / Tanks-and-Temples protocols do before
+    they measure it: the mesh's depth is rendered from every view (render_mesh_depth), a vertex is kept when at
+    least min_views views see it -- inside the image, in front of the camera, and at a depth c <= depth[pixel]
+    (1 + tol_rel) + tol_abs of the pixel nearest to it -- and a triangle when its three corners are.  Returns
+    (vertices' [V', 3], triangles' int32 [T', 3] renumbered, kept_vertices int32 [V'], the original ids ascending),
+    as ops.mesh_clean does; the order of what is kept is unchanged.  The tolerance covers the depth a slanted
+    surface gains over half a pixel; the defaults are 1 % relative, nothing absolute."""
+    from . import ops
+    h, w = (int(x) for x in resolution)
+    near = ops.MESH_NEAR if near is None else near
+    proj = view_projections(views, (h, w), transform, vertices.device)
+    depth, _ = ops.mesh_raster(vertices, triangles, proj, h, w, near=near)
+    count = ops.mesh_visibility(vertices, proj, h, w, depth=depth, tol_abs=tol_abs, tol_rel=tol_rel, near=near)
+    return ops.mesh_cull(vertices, triangles, count >= int(min_views))

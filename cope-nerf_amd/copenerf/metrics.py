@@ -475,7 +475,8 @@ def geometry_from_stats(pred, gt, area):
 
 
 def mesh_geometry_metrics(vertices, triangles, gt_points, *, threshold, max_dist=math.inf, n_samples=None,
-                          density=None, seed=0, transform=None, crop_min=None, crop_max=None):
+                          density=None, seed=0, transform=None, crop_min=None, crop_max=None, cull_views=None,
+                          cull_resolution=None, cull_gt=False, cull_min_views=1, cull_tol_abs=None, cull_tol_rel=None):
     """Geometry metrics of a triangle mesh against a ground-truth cloud, all on the device.  vertices fp32
     [V, 3], triangles int32 [T, 3] (NeuSRenderer.extract_geometry's output as it is) and gt_points fp32 [N, 3]
     are device tensors.  The mesh is sampled uniformly by area (cn_mesh_area / cn_mesh_sample, Philox seed
@@ -488,9 +489,19 @@ def mesh_geometry_metrics(vertices, triangles, gt_points, *, threshold, max_dist
                     farther than max_dist is a miss);  fscore = 2 P R / (P + R), 0 when P + R = 0;
       n_pred, n_gt, n_pred_far, n_gt_far  the points counted on either side and those beyond max_dist;  area.
     The samples and the distances stay on the device; what comes back is the area (8 bytes), the two
-    bounding boxes and two double [4] statistics."""
+    bounding boxes and two double [4] statistics.
+    cull_views / cull_resolution (together): the views -- dicts with "camera_mat", "world_mat" and optionally
+    "scale_mat", as evaluate takes them, in the mesh's own frame -- and their (h, w).  The mesh is first cut down
+    to what at least cull_min_views of them see (mesh.cull_mesh with cull_tol_abs / cull_tol_rel, by default
+    cull_mesh's), before `transform` and before sampling, as the ScanNet / DTU / Tanks-and-Temples protocols do.
+    cull_gt drops the ground-truth points outside every view's frustum, the cameras taken through `transform`
+    into the ground truth's frame.  Without them nothing changes."""
     if (n_samples is None) == (density is None):
         raise ValueError("mesh_geometry_metrics: exactly one of n_samples and density")
+    if (cull_views is None) != (cull_resolution is None):
+        raise ValueError("mesh_geometry_metrics: cull_views and cull_resolution together")
+    if cull_gt and cull_views is None:
+        raise ValueError("mesh_geometry_metrics: cull_gt needs cull_views")
     if (crop_min is None) != (crop_max is None):
         raise ValueError("mesh_geometry_metrics: crop_min and crop_max together")
     if not threshold > 0 or not max_dist > 0:
@@ -499,6 +510,15 @@ def mesh_geometry_metrics(vertices, triangles, gt_points, *, threshold, max_dist
     ops._need_cloud("mesh_geometry_metrics", triangles, "triangles", dtype=torch.int32)
     ops._need_cloud("mesh_geometry_metrics", gt_points, "gt_points")
     dev = vertices.device
+    if cull_views is not None:
+        from . import mesh
+        tol = {k: v for k, v in (("tol_abs", cull_tol_abs), ("tol_rel", cull_tol_rel)) if v is not None}
+        vertices, triangles, _ = mesh.cull_mesh(vertices, triangles, cull_views, cull_resolution,
+                                                min_views=cull_min_views, **tol)
+        if cull_gt:
+            h, w = (int(x) for x in cull_resolution)
+            seen = ops.mesh_visibility(gt_points, mesh.view_projections(cull_views, (h, w), transform, dev), h, w)
+            gt_points = gt_points[seen > 0].contiguous()
     if transform is not None:
         M = torch.as_tensor(np.asarray(transform.detach().cpu() if torch.is_tensor(transform) else transform,
                                        dtype=np.float64), dtype=torch.float32).to(dev)

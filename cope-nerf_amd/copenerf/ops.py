@@ -1296,6 +1296,44 @@ def mesh_clean(vertices, triangles, keep_largest=False, min_triangles=0, stats=N
     return vertices.index_select(0, kept.long()), tri, kept
 
 
+def mesh_select_mask(triangles, vmask):
+    """mesh_select from a per-vertex mask -- cn_mesh_select_mask: (descriptor, workspace, counts) as mesh_select
+    returns them, for mesh_compact.  vmask: a bool or uint8 [V] device tensor, not 0 where the vertex is kept; a
+    triangle is kept when its three corners are."""
+    if vmask.dtype == torch.bool:
+        vmask = vmask.to(torch.uint8)
+    if not vmask.is_cuda or vmask.dtype != torch.uint8 or vmask.dim() != 1 or not vmask.is_contiguous():
+        raise RuntimeError("mesh_select_mask: vmask must be a contiguous bool or uint8 [V] device tensor")
+    d = _mesh_clean_desc("mesh_select_mask", triangles, vmask.shape[0])
+    if triangles.device != vmask.device:
+        raise RuntimeError("mesh_select_mask: triangles and vmask on different devices")
+    dev = triangles.device
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    d.counts = _ptr(counts)
+    lib = _lib.load()
+    ws = torch.empty(max(int(lib.cn_mesh_clean_workspace_bytes(d.V, d.T)), 1), dtype=torch.uint8, device=dev)
+    _lib.check(lib.cn_mesh_select_mask(ctypes.byref(d), _ptr(vmask) if d.V else None, _ptr(ws), ws.numel(), _stream()),
+               "cn_mesh_select_mask")
+    # cn_mesh_compact's checks want the two arrays of the component pass; it reads neither
+    d.label = d.tri_count = _ptr(ws) if d.V else None
+    return d, ws, counts
+
+
+def mesh_cull(vertices, triangles, keep_mask):
+    """The mesh without the vertices whose keep_mask (bool or uint8 [V]) is 0 and without the triangles that had
+    one as a corner.  Returns what mesh_clean returns: (vertices' [V', 3], triangles' int32 [T', 3] renumbered,
+    kept_vertices int32 [V']: the original ids, ascending); kept vertices and triangles keep their order."""
+    _need(vertices, "vertices")
+    if keep_mask.shape[0] != vertices.shape[0]:
+        raise RuntimeError(f"mesh_cull: a mask of {keep_mask.shape[0]} for {vertices.shape[0]} vertices")
+    d, ws, counts = mesh_select_mask(triangles, keep_mask)
+    Vk, Tk = (int(c) for c in counts.tolist())
+    kept = torch.empty(Vk, dtype=torch.int32, device=triangles.device)
+    tri = torch.empty(Tk, 3, dtype=torch.int32, device=triangles.device)
+    mesh_compact(d, ws, kept, tri, (Vk, Tk))
+    return vertices.index_select(0, kept.long()), tri, kept
+
+
 # ---------------------------------------------------------------------------
 # Mesh geometry metrics (additive to ABI v22): cn_mesh_eval.hip
 NN_MAX_CELLS = 1 << 26
@@ -1425,6 +1463,77 @@ def cloud_stats(dist, threshold, max_dist=math.inf, points=None, crop_min=None, 
     ws = _workspace(lib.cn_cloud_stats_workspace_bytes(d.Q), dev)
     _lib.check(lib.cn_cloud_stats(ctypes.byref(d), _ptr(ws), ws.numel(), _stream()), "cn_cloud_stats")
     return out
+
+
+# ---------------------------------------------------------------------------
+# Mesh depth rendering and visibility (additive to ABI v22): cn_mesh_raster.hip
+MESH_NEAR = 1e-4  # the default near bound on a corner's (or a point's) depth c
+
+
+def _need_proj(fn, proj, dev):
+    _need(proj, "proj", ndim=0)
+    if proj.dtype != torch.float32 or proj.dim() != 3 or tuple(proj.shape[1:]) != (3, 4) or not proj.is_contiguous():
+        raise RuntimeError(f"{fn}: proj must be a contiguous fp32 [N, 3, 4] device tensor (got {proj.dtype}, "
+                           f"shape {tuple(proj.shape)})")
+    if proj.device != dev:
+        raise RuntimeError(f"{fn}: proj on another device")
+
+
+def mesh_raster(vertices, triangles, proj, h, w, near=MESH_NEAR, view_batch=0, pixel_budget=0, stats=None):
+    """Depth rendering of an indexed triangle mesh -- cn_mesh_raster: (depth fp32 [N, h, w], +inf where nothing is
+    seen; tri int32 [N, h, w], the triangle seen, -1 where none) of vertices fp32 [V, 3] / triangles int32 [T, 3]
+    under the projections proj fp32 [N, 3, 4] (copenerf.mesh.camera_projection).  Two-sided inclusive coverage of
+    pixel centres without cracks along shared edges, perspective-correct depth, the nearest triangle wins and equal
+    depths go to the smaller id; a triangle with a corner at depth < near is skipped (no clipping).  view_batch /
+    pixel_budget: 0 for the library's defaults (8 views per pass; boxes of up to 64 pixels walked by one thread).
+    stats: an optional dict that receives thread_pairs / group_pairs, the (triangle, view) pairs each path walked
+    (one 16-byte read-back)."""
+    _need_cloud("mesh_raster", vertices, "vertices")
+    _need_cloud("mesh_raster", triangles, "triangles", dtype=torch.int32)
+    dev = vertices.device
+    if triangles.device != dev:
+        raise RuntimeError("mesh_raster: vertices and triangles on different devices")
+    _need_proj("mesh_raster", proj, dev)
+    d = _lib.MeshRasterDesc()
+    d.V, d.T, d.N, d.h, d.w = vertices.shape[0], triangles.shape[0], proj.shape[0], int(h), int(w)
+    d.view_batch, d.near, d.pixel_budget = int(view_batch), float(near), int(pixel_budget)
+    if d.h < 1 or d.w < 1:
+        raise RuntimeError(f"mesh_raster: image {d.h} x {d.w}")
+    d.vertices, d.triangles = _ptr(vertices) if d.V else None, _ptr(triangles) if d.T else None
+    depth = torch.empty(d.N, d.h, d.w, dtype=torch.float32, device=dev)
+    tri = torch.empty(d.N, d.h, d.w, dtype=torch.int32, device=dev)
+    counters = torch.zeros(2, dtype=torch.int64, device=dev) if stats is not None else None
+    d.proj, d.depth, d.tri, d.stats = (_ptr(proj), _ptr(depth), _ptr(tri), _ptr(counters)) if d.N else (None,) * 4
+    lib = _lib.load()
+    ws = _workspace(lib.cn_mesh_raster_workspace_bytes(d.V, d.T, d.N, d.h, d.w, d.view_batch), dev)
+    _lib.check(lib.cn_mesh_raster(ctypes.byref(d), _ptr(ws), ws.numel(), _stream()), "cn_mesh_raster")
+    if stats is not None:
+        stats["thread_pairs"], stats["group_pairs"] = (int(c) for c in counters.tolist())
+    return depth, tri
+
+
+def mesh_visibility(points, proj, h, w, depth=None, tol_abs=0.0, tol_rel=0.0, near=MESH_NEAR):
+    """count int32 [Q]: the views that see each of points fp32 [Q, 3] -- cn_mesh_visibility.  A view sees a point
+    at depth c >= near whose pixel (rounded to the nearest centre) lies inside the h x w image and, with depth
+    fp32 [N, h, w] (mesh_raster's), c <= depth[pixel] (1 + tol_rel) + tol_abs.  Without depth: the frustum test."""
+    _need_cloud("mesh_visibility", points, "points")
+    dev = points.device
+    _need_proj("mesh_visibility", proj, dev)
+    d = _lib.MeshVisibilityDesc()
+    d.Q, d.N, d.h, d.w, d.near = points.shape[0], proj.shape[0], int(h), int(w), float(near)
+    d.tol_abs, d.tol_rel = float(tol_abs), float(tol_rel)
+    if depth is not None:
+        _need(depth, "depth", ndim=0)
+        if depth.dtype != torch.float32 or tuple(depth.shape) != (d.N, d.h, d.w) or not depth.is_contiguous() or \
+                depth.device != dev:
+            raise RuntimeError(f"mesh_visibility: depth must be a contiguous fp32 [{d.N}, {d.h}, {d.w}] tensor on the "
+                               f"points' device (got {depth.dtype}, shape {tuple(depth.shape)})")
+        d.depth = _ptr(depth) if d.N else None
+    count = torch.empty(d.Q, dtype=torch.int32, device=dev)
+    d.points, d.count = (_ptr(points), _ptr(count)) if d.Q else (None, None)
+    d.proj = _ptr(proj) if d.N else None
+    _lib.call("cn_mesh_visibility", ctypes.byref(d), _stream())
+    return count
 
 
 # ---------------------------------------------------------------------------

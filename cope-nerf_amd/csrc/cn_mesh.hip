@@ -468,6 +468,21 @@ __global__ void select_flags_kernel(CleanArgs a) {
     if (i < a.T) a.tflag[i] = root_kept(a, tri_root(a, i)) ? 1 : 0;
 }
 
+// the same flags from a caller's per-vertex mask: a triangle is kept when its three corners are
+__global__ void select_mask_flags_kernel(CleanArgs a, const uint8_t* __restrict__ vmask) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < a.V) a.vflag[i] = vmask[i] ? 1 : 0;
+    if (i < a.T) {
+        bool keep = true;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const int c = a.tri[(int64_t)i * 3 + j];
+            keep = keep && (unsigned)c < (unsigned)a.V && vmask[c];
+        }
+        a.tflag[i] = keep ? 1 : 0;
+    }
+}
+
 __global__ void compact_kernel(CleanArgs a) {
     // output buffers smaller than the counts: nothing is written (the decision is the same in every thread)
     if (a.counts[0] > a.max_vertices || a.counts[1] > a.max_triangles) return;
@@ -737,6 +752,28 @@ extern "C" int cn_mesh_select(const cn_mesh_clean_desc* d, void* workspace, int6
     // (an empty list scans one empty tile: the counts are written as zeros)
     if ((rc = scan_launch<false>("cn_mesh_select", p.vflag, d->V, p.vt, p.vtot, p.voff, d->counts, st))) return rc;
     return scan_launch<false>("cn_mesh_select", p.tflag, d->T, p.tt, p.ttot, p.toff, d->counts + 1, st);
+}
+
+extern "C" int cn_mesh_select_mask(const cn_mesh_clean_desc* d, const uint8_t* vmask, void* workspace, int64_t workspace_bytes,
+                                   cn_stream_t stream) {
+    int rc = clean_check("cn_mesh_select_mask", d, false);
+    if (rc) return rc;
+    CN_REQUIRE(d->V == 0 || vmask, CN_ERR_ARG, "cn_mesh_select_mask: null vmask");
+    CN_REQUIRE(d->counts, CN_ERR_ARG, "cn_mesh_select_mask: null counts");
+    CN_REQUIRE(((uintptr_t)d->counts & 7) == 0, CN_ERR_ALIGN, "cn_mesh_select_mask: counts 8-byte aligned");
+    const size_t need = clean_plan(d->V, d->T, nullptr).bytes;
+    CN_REQUIRE(workspace && workspace_bytes >= 0 && (size_t)workspace_bytes >= need, CN_ERR_SHAPE,
+               "cn_mesh_select_mask: workspace %lld bytes, %zu needed", (long long)workspace_bytes, need);
+    CN_REQUIRE(((uintptr_t)workspace & (kAlign - 1)) == 0, CN_ERR_ALIGN, "cn_mesh_select_mask: workspace not 256-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const CleanPlan p = clean_plan(d->V, d->T, workspace);
+    const int n = d->V > d->T ? d->V : d->T;
+    if (n > 0) {
+        select_mask_flags_kernel<<<(n + 255) / 256, 256, 0, st>>>(clean_args(d, p), vmask);
+        if ((rc = check_launch("cn_mesh_select_mask"))) return rc;
+    }
+    if ((rc = scan_launch<false>("cn_mesh_select_mask", p.vflag, d->V, p.vt, p.vtot, p.voff, d->counts, st))) return rc;
+    return scan_launch<false>("cn_mesh_select_mask", p.tflag, d->T, p.tt, p.ttot, p.toff, d->counts + 1, st);
 }
 
 extern "C" int cn_mesh_compact(const cn_mesh_clean_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream) {

@@ -949,6 +949,14 @@ int cn_mesh_component_sizes(const cn_mesh_clean_desc* d, cn_stream_t stream);
 size_t cn_mesh_clean_workspace_bytes(int32_t V, int32_t T);
 int cn_mesh_select(const cn_mesh_clean_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
 int cn_mesh_compact(const cn_mesh_clean_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+/* cn_mesh_select_mask (additive to ABI v22): cn_mesh_select's workspace and counts from a
+ * caller's per-vertex mask instead of components: vertex v is kept when vmask[v] (DEVICE
+ * uint8 [V]) is not 0, a triangle when all three corners are inside [0, V) and kept.  The
+ * same scans, the same counts = (V', T'), the same workspace layout, so cn_mesh_compact
+ * finishes it unchanged (its checks still want label and tri_count non-NULL and 4-byte
+ * aligned; it reads neither, and neither does this entry).  Reads V, T, triangles, counts. */
+int cn_mesh_select_mask(const cn_mesh_clean_desc* d, const uint8_t* vmask, void* workspace, int64_t workspace_bytes,
+                        cn_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
  * Mesh geometry metrics (additive to ABI v22): Chamfer distance and precision / recall /
@@ -1056,6 +1064,68 @@ typedef struct cn_cloud_stats_desc {
 } cn_cloud_stats_desc;
 size_t cn_cloud_stats_workspace_bytes(int64_t Q);
 int cn_cloud_stats(const cn_cloud_stats_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
+ * Mesh depth rendering and visibility (additive to ABI v22): what the ScanNet / DTU /
+ * Tanks-and-Temples protocols cull a predicted mesh with before they measure it.  The
+ * reference has no rasteriser; the yardstick is a float64 restatement.  A camera is a 3 x 4
+ * projection P (fp32, row-major): (a, b, c) = P [X, 1] puts X at pixel (a / c, b / c), pixel
+ * centres at integers, at depth c (> 0 in front of the camera).
+ *
+ * cn_mesh_raster: depth [N][h][w] (+inf where nothing is seen) and tri [N][h][w] (the
+ * triangle seen, -1 where none) of vertices [V][3] fp32 / triangles [T][3] int32 under proj
+ * [N][3][4].  Per vertex, in fp32 and this order: a = ((P00 x + P01 y) + P02 z) + P03 (b, c
+ * alike), sx = a / c, sy = b / c, iw = 1 / c.  The edge function of an edge at pixel p is
+ * E = (hx - lx)(py - ly) - (hy - ly)(px - lx) with l its corner of the smaller vertex index,
+ * negated for the triangle that runs the edge from the larger index: two triangles that share
+ * an edge get the same value with opposite signs, so no pixel centre falls between them.  A
+ * pixel centre is covered when the three edge values e0, e1, e2 (ek opposite corner k) are all
+ * >= 0 or all <= 0 (two-sided, inclusive); its depth is ((e0 + e1) + e2) / ((e0 iw0 + e1 iw1)
+ * + e2 iw2), i.e. 1 / c interpolated linearly in screen space.  The smallest depth wins, equal
+ * depths go to the smaller triangle id (a 64-bit atomicMin over (depth bits, id)): the images
+ * do not depend on scheduling.  A triangle with a corner index outside [0, V), zero screen
+ * area, or any corner at c < near (or not finite) is skipped in that view -- there is no
+ * clipping.  The bounding box is clamped to the image.  A triangle whose box holds at most
+ * pixel_budget pixels (0: 64) is walked by one thread; a larger one goes onto a list and is
+ * walked by a whole workgroup in a second launch.  Views are processed view_batch (0: 8) at a
+ * time, fewer where T x batch or h w x batch would reach 2^31.  stats (DEVICE int64 [2], or
+ * NULL) receives the (triangle, view) pairs walked by a thread and by a workgroup.
+ * Workspace (256-byte aligned), with B the batch, each rounded up to 256 bytes: 8 B h w (the
+ * z-buffer) + 16 B V (projected vertices) + 8 B T (the list: room for every pair, it cannot
+ * overflow) + 4.  V, T, h w < 2^31; near > 0.
+ * ------------------------------------------------------------------------ */
+typedef struct cn_mesh_raster_desc {
+    int64_t V, T;
+    const float* vertices;              /* [V][3] */
+    const int32_t* triangles;           /* [T][3] */
+    int32_t N, h, w;
+    int32_t view_batch;                 /* 0: 8 */
+    const float* proj;                  /* [N][3][4] */
+    float near;
+    int32_t pixel_budget;               /* 0: 64 */
+    float* depth;                       /* [N][h][w] */
+    int32_t* tri;                       /* [N][h][w] */
+    int64_t* stats;                     /* device [2], or NULL */
+} cn_mesh_raster_desc;
+size_t cn_mesh_raster_workspace_bytes(int64_t V, int64_t T, int32_t N, int32_t h, int32_t w, int32_t view_batch);
+int cn_mesh_raster(const cn_mesh_raster_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+
+/* cn_mesh_visibility: count [Q] = the views that see each of points [Q][3], one thread per
+ * point, no atomics.  A view sees a point when c >= near, the pixel (floor(a / c + 0.5),
+ * floor(b / c + 0.5)) lies inside the h x w image and, with depth [N][h][w] given (cn_mesh_raster's),
+ * c <= depth[pixel] (1 + tol_rel) + tol_abs (fp32: one product, one sum; a pixel that shows
+ * nothing, +inf, hides nothing).  depth = NULL: the frustum test alone.  No workspace. */
+typedef struct cn_mesh_visibility_desc {
+    int64_t Q;
+    const float* points;                /* [Q][3] */
+    int32_t N, h, w;
+    float near;
+    const float* proj;                  /* [N][3][4] */
+    const float* depth;                 /* [N][h][w], or NULL */
+    float tol_abs, tol_rel;
+    int32_t* count;                     /* [Q] */
+} cn_mesh_visibility_desc;
+int cn_mesh_visibility(const cn_mesh_visibility_desc* d, cn_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
  * Pose refinement (ABI v17): compute_loss_and_warp_image

@@ -3,13 +3,20 @@ precision / recall / F-score at a threshold in the Tanks and Temples style (metr
 
     python tools/evaluate_mesh.py MESH.ply GT.ply --threshold T [--max-dist D] (--samples S | --density RHO)
         [--seed N] [--crop-min X Y Z --crop-max X Y Z] [--transform T.npy | --align-poses PRED.npy GT.npy]
-        [--out results.txt]
+        [--cull-views K.npy W2C.npy [SCALE.npy] --cull-resolution H W [--cull-min-views N] [--cull-tol-abs A]
+         [--cull-tol-rel R] [--cull-gt]] [--depths-out DIR] [--culled-out MESH.ply] [--out results.txt]
 
 MESH.ply is a triangle mesh (tools/extract_mesh.py's output as it is), GT.ply a point cloud (a mesh's vertices are
 taken as the cloud).  --transform is a 4 x 4 similarity applied to the mesh first.  --align-poses takes two
 camera-to-world trajectories [N, 3 or 4, 4] (.npy) and applies the Sim(3) that aligns the camera centres of PRED
 to those of GT (metrics.align_ate_c2b_use_a2b / umeyama, the alignment compute_ATE is measured under): a pose-free
-reconstruction lives in its own gauge.  Prints one `name: value` line per metric and with --out writes them in
+reconstruction lives in its own gauge.  --cull-views cuts the mesh down to what the cameras saw before it is
+measured (mesh.cull_mesh: the ScanNet / DTU / Tanks-and-Temples protocols): camera matrices K [N, 4, 4] or [4, 4],
+world-to-camera matrices [N, 4, 4] and optionally scale matrices [N, 4, 4] or [4, 4], in the mesh's own frame, for
+images of --cull-resolution; --cull-gt also drops the ground-truth points outside every frustum.  --depths-out
+writes the mesh's depth from every view as DIR/depth_%06d.npz (key `pred`, 0 where nothing is seen: what
+pose_refine.load_depth_dir reads and metrics.depth_metrics scores against sensor depth), --culled-out the culled
+mesh.  Prints one `name: value` line per metric and with --out writes them in
 metrics.write_results' format."""
 import argparse
 import os
@@ -35,6 +42,24 @@ def pose_alignment(pred_poses, gt_poses):
     return M
 
 
+def load_views(paths):
+    """The views of --cull-views: camera matrices [N, 4, 4] or one [4, 4] for all, world-to-camera matrices
+    [N, 4, 4], and optionally scale matrices [N, 4, 4] or one [4, 4]."""
+    mats = [np.asarray(np.load(p), dtype=np.float64) for p in paths]
+    W = mats[1]
+    if W.ndim != 3 or W.shape[1:] != (4, 4):
+        raise SystemExit(f"evaluate_mesh: {paths[1]}: world-to-camera matrices [N, 4, 4], got {W.shape}")
+    views = [{"world_mat": w} for w in W]
+    for key, m, p in (("camera_mat", mats[0], paths[0]),) + ((("scale_mat", mats[2], paths[2]),) if len(mats) == 3 else ()):
+        if m.shape == (4, 4):
+            m = np.broadcast_to(m, W.shape)
+        if m.shape != W.shape:
+            raise SystemExit(f"evaluate_mesh: {p}: [4, 4] or {W.shape}, got {m.shape}")
+        for v, x in zip(views, m):
+            v[key] = x
+    return views
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("mesh")
@@ -50,8 +75,22 @@ def main(argv=None):
     g = ap.add_mutually_exclusive_group()
     g.add_argument("--transform")
     g.add_argument("--align-poses", nargs=2, metavar=("PRED.npy", "GT.npy"))
+    ap.add_argument("--cull-views", nargs="+", metavar="NPY")
+    ap.add_argument("--cull-resolution", type=int, nargs=2, metavar=("H", "W"))
+    ap.add_argument("--cull-min-views", type=int, default=1)
+    ap.add_argument("--cull-tol-abs", type=float)
+    ap.add_argument("--cull-tol-rel", type=float)
+    ap.add_argument("--cull-gt", action="store_true")
+    ap.add_argument("--depths-out")
+    ap.add_argument("--culled-out")
     ap.add_argument("--out")
     a = ap.parse_args(argv)
+    if a.cull_views is not None and len(a.cull_views) not in (2, 3):
+        ap.error("--cull-views takes K.npy W2C.npy [SCALE.npy]")
+    if (a.cull_views is None) != (a.cull_resolution is None):
+        ap.error("--cull-views and --cull-resolution go together")
+    if a.cull_views is None and (a.cull_gt or a.depths_out or a.culled_out):
+        ap.error("--cull-gt, --depths-out and --culled-out need --cull-views")
     if not torch.cuda.is_available():
         raise SystemExit("evaluate_mesh: needs a HIP device; the metrics have no CPU path")
     from copenerf import metrics
@@ -66,10 +105,26 @@ def main(argv=None):
     elif a.align_poses:
         transform = pose_alignment(np.load(a.align_poses[0]), np.load(a.align_poses[1]))
     dev = torch.device("cuda")
+    tv, tf = torch.from_numpy(vertices).to(dev), torch.from_numpy(triangles).to(dev)
+    cull = {}
+    if a.cull_views:
+        from copenerf import mesh
+        views = load_views(a.cull_views)
+        tol = {k: v for k, v in (("tol_abs", a.cull_tol_abs), ("tol_rel", a.cull_tol_rel)) if v is not None}
+        cull = dict(cull_views=views, cull_resolution=tuple(a.cull_resolution), cull_gt=a.cull_gt,
+                    cull_min_views=a.cull_min_views, **{"cull_" + k: v for k, v in tol.items()})
+        if a.depths_out:
+            os.makedirs(a.depths_out, exist_ok=True)
+            depth = mesh.render_mesh_depth(tv, tf, views, a.cull_resolution)["depth"]
+            depth = torch.where(torch.isinf(depth), torch.zeros_like(depth), depth).cpu().numpy()
+            for i, d in enumerate(depth):
+                np.savez(os.path.join(a.depths_out, "depth_%06d.npz" % i), pred=d)
+        if a.culled_out:
+            cv, cf, _ = mesh.cull_mesh(tv, tf, views, a.cull_resolution, min_views=a.cull_min_views, **tol)
+            mesh.write_ply(a.culled_out, cv.cpu().numpy(), cf.cpu().numpy())
     result = metrics.mesh_geometry_metrics(
-        torch.from_numpy(vertices).to(dev), torch.from_numpy(triangles).to(dev), torch.from_numpy(gt).to(dev),
-        threshold=a.threshold, max_dist=a.max_dist, n_samples=a.samples, density=a.density, seed=a.seed,
-        transform=transform, crop_min=a.crop_min, crop_max=a.crop_max)
+        tv, tf, torch.from_numpy(gt).to(dev), threshold=a.threshold, max_dist=a.max_dist, n_samples=a.samples,
+        density=a.density, seed=a.seed, transform=transform, crop_min=a.crop_min, crop_max=a.crop_max, **cull)
     for key, value in result.items():
         print(f"{key}: {value}")
     if a.out:
