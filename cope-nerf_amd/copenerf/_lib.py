@@ -225,6 +225,23 @@ class MeshVisibilityDesc(ctypes.Structure):
     ]
 
 
+class MeshShadeDesc(ctypes.Structure):
+    _fields_ = [
+        ("V", c_i64), ("T", c_i64), ("vertices", c_ptr), ("triangles", c_ptr), ("N", c_i32), ("h", c_i32), ("w", c_i32),
+        ("C", c_i32), ("proj", c_ptr), ("tri", c_ptr), ("attr", c_ptr), ("vnormals", c_ptr), ("rot", c_ptr),
+        ("fill", c_f32), ("ambient", c_f32), ("light", c_f32 * 3), ("grey", c_f32), ("albedo_from_attr", c_i32),
+        ("background", ctypes.c_uint8 * 3), ("attr_out", c_ptr), ("normal_out", c_ptr), ("normal_img", c_ptr),
+        ("shaded_img", c_ptr),
+    ]
+
+
+class CloudNormalStatsDesc(ctypes.Structure):
+    _fields_ = [
+        ("Q", c_i64), ("N", c_i64), ("query_normals", c_ptr), ("target_normals", c_ptr), ("index", c_ptr), ("dist", c_ptr),
+        ("points", c_ptr), ("crop_min", c_f32 * 3), ("crop_max", c_f32 * 3), ("max_dist", c_f32), ("out", c_ptr),
+    ]
+
+
 LPIPS_CONVS, LPIPS_TAPS = 13, 5
 
 
@@ -336,10 +353,13 @@ SIGNATURES = {
     "cn_nn_query": (c_i32, [ctypes.POINTER(NnQueryDesc), c_ptr]),
     "cn_cloud_stats_workspace_bytes": (ctypes.c_size_t, [c_i64]),
     "cn_cloud_stats": (c_i32, [ctypes.POINTER(CloudStatsDesc), c_ptr, c_i64, c_ptr]),
+    "cn_cloud_normal_stats_workspace_bytes": (ctypes.c_size_t, [c_i64]),
+    "cn_cloud_normal_stats": (c_i32, [ctypes.POINTER(CloudNormalStatsDesc), c_ptr, c_i64, c_ptr]),
     "cn_mesh_select_mask": (c_i32, [ctypes.POINTER(MeshCleanDesc), c_ptr, c_ptr, c_i64, c_ptr]),
     "cn_mesh_raster_workspace_bytes": (ctypes.c_size_t, [c_i64, c_i64, c_i32, c_i32, c_i32, c_i32]),
     "cn_mesh_raster": (c_i32, [ctypes.POINTER(MeshRasterDesc), c_ptr, c_i64, c_ptr]),
     "cn_mesh_visibility": (c_i32, [ctypes.POINTER(MeshVisibilityDesc), c_ptr]),
+    "cn_mesh_shade": (c_i32, [ctypes.POINTER(MeshShadeDesc), c_ptr]),
     "cn_refine_workspace_bytes":(ctypes.c_size_t, [c_i32, c_i32, c_i32]),
     "cn_refine_warp": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
                                c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
@@ -349,6 +369,8 @@ SIGNATURES = {
     "cn_depth_errors_workspace_bytes": (ctypes.c_size_t, [c_i32, c_i32, c_i32]),
     "cn_depth_errors": (c_i32, [c_i32, c_i32, c_i32, c_ptr, c_i32, c_i32, c_ptr, c_ptr, c_f32, c_f32, c_i32, c_ptr,
                                 c_ptr, c_i64, c_ptr]),
+    "cn_normal_errors_workspace_bytes": (ctypes.c_size_t, [c_i64]),
+    "cn_normal_errors": (c_i32, [c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
     "cn_ray_visuals_workspace_bytes": (ctypes.c_size_t, [c_i32]),
     "cn_ray_visuals": (c_i32, [c_i32, c_i32, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i32, c_ptr, c_ptr, c_f32, c_ptr,
                                c_ptr, ctypes.POINTER(c_f32), c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),

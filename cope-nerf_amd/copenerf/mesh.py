@@ -2,7 +2,8 @@
 meshes through trimesh, which this package does not depend on) and the reader the geometry metrics load
 meshes and ground-truth clouds with; and what turns a mesh back into per-view depth: camera_projection (the
 project's camera convention as one 3 x 4 matrix), render_mesh_depth and cull_mesh (the view-based cull of the
-ScanNet / DTU / Tanks-and-Temples protocols) over ops.mesh_raster / mesh_visibility / mesh_cull."""
+ScanNet / DTU / Tanks-and-Temples protocols) over ops.mesh_raster / mesh_visibility / mesh_cull, and render_mesh
+(normal maps, vertex attributes and shaded pictures over ops.mesh_shade)."""
 from __future__ import annotations
 
 import numpy as np
@@ -239,3 +240,68 @@ def cull_mesh(vertices, triangles, views, resolution, min_views=1, tol_abs=CULL_
     depth, _ = ops.mesh_raster(vertices, triangles, proj, h, w, near=near)
     count = ops.mesh_visibility(vertices, proj, h, w, depth=depth, tol_abs=tol_abs, tol_rel=tol_rel, near=near)
     return ops.mesh_cull(vertices, triangles, count >= int(min_views))
+
+
+def _similarity(transform, device):
+    """(M fp32 [4, 4] on the device, R float64 [3, 3]: the rotation of the similarity M) or (None, None)."""
+    import torch
+    if transform is None:
+        return None, None
+    M = _mat4(transform, "transform")
+    A = M[:3, :3]
+    s = abs(np.linalg.det(A)) ** (1.0 / 3.0)
+    if not s > 0.0:
+        raise ValueError("transform must be invertible")
+    return torch.as_tensor(M, dtype=torch.float32).to(device), A / s
+
+
+def render_mesh(vertices, triangles, views, resolution, *, normals=None, colors=None, attrs=None, frame="camera",
+                light=(0, 0, 1), ambient=0.3, background=(255, 255, 255), transform=None, near=None):
+    """A mesh seen from every view, on the device (ops.mesh_raster, then ops.mesh_shade on its triangle image):
+      "depth", "tri"   as render_mesh_depth returns them;
+      "normal"         fp32 [N, h, w, 3], the unit surface normal turned towards the camera, zero where nothing is
+                       seen: the triangles' own normals, or with normals fp32 [V, 3] the interpolated vertex normals;
+      "normal_image"   uint8 [N, h, w, 3], normal * 128 + 128: what visualize writes as _normal.png;
+      "shaded"         uint8 [N, h, w, 3], albedo (ambient + (1 - ambient) max(0, normal . light)), the albedo from
+                       colors (uint8, or float in [0, 1], [V, 3]) or a constant grey; `background` elsewhere;
+      "attr"           fp32 [N, h, w, C] with attrs fp32 [V, C] (1 <= C <= 16): perspective-correct interpolation.
+    frame="camera" gives the normals in each view's camera frame (world_mat[:3, :3] n, the frame of
+    inference.render_image's "normal"), "world" leaves them in the mesh's.  light is normalised here and lives in
+    the normals' frame: (0, 0, 1) in the camera frame is a headlight.  transform: a 4 x 4 similarity applied to the
+    vertices, and its rotation to normals, before anything else (as metrics.mesh_geometry_metrics does), the cameras
+    following it; camera-frame normals are unchanged by it."""
+    import torch
+    from . import ops
+    if frame not in ("camera", "world"):
+        raise ValueError(f"render_mesh: frame {frame!r} (camera or world)")
+    h, w = (int(x) for x in resolution)
+    dev = vertices.device
+    M, R = _similarity(transform, dev)
+    if M is not None:
+        vertices = (vertices @ M[:3, :3].T + M[:3, 3]).contiguous()
+        if normals is not None:
+            normals = (normals @ torch.as_tensor(R, dtype=torch.float32).to(dev).T).contiguous()
+    proj = view_projections(views, (h, w), transform, dev)
+    depth, tri = ops.mesh_raster(vertices, triangles, proj, h, w, near=ops.MESH_NEAR if near is None else near)
+    rot = None
+    if frame == "camera":
+        rots = [_mat4(v["world_mat"], "world_mat")[:3, :3] @ (R.T if R is not None else np.eye(3)) for v in views]
+        rot = torch.as_tensor(np.stack(rots) if rots else np.zeros((0, 3, 3)), dtype=torch.float32).to(dev).contiguous()
+    L = np.asarray(light, dtype=np.float64)
+    if L.shape != (3,) or not np.linalg.norm(L) > 0.0:
+        raise ValueError(f"render_mesh: light {light}")
+    L = L / np.linalg.norm(L)
+    albedo = None
+    if colors is not None:
+        albedo = colors.to(dev)
+        albedo = albedo.float() / 255.0 if albedo.dtype == torch.uint8 else albedo.float()
+        if albedo.dim() != 2 or tuple(albedo.shape) != (vertices.shape[0], 3):
+            raise ValueError(f"render_mesh: colors {tuple(colors.shape)} for {vertices.shape[0]} vertices")
+        albedo = albedo.contiguous()
+    out = ops.mesh_shade(vertices, triangles, proj, tri, attr=albedo, vnormals=normals, rot=rot,
+                         want=("normal", "normal_image", "shaded"), light=L, ambient=ambient,
+                         albedo_from_attr=albedo is not None, background=background)
+    if attrs is not None:
+        out["attr"] = ops.mesh_shade(vertices, triangles, proj, tri, attr=attrs, want=("attr",))["attr"]
+    out["depth"], out["tri"] = depth, tri
+    return out

@@ -314,6 +314,39 @@ def compute_depth_errors(gt_depth_map, pred_depth_map, min_depth=0.1, max_depth=
 
 
 # ---------------------------------------------------------------------------
+# normal metrics
+NORMAL_KEYS = ("mean", "median", "rmse", "a11.25", "a22.5", "a30")
+
+
+def normal_metrics(pred, gt, mask=None):
+    """The angular error between normal maps, the table of the surface-normal literature: pred, gt [h, w, 3] or
+    [B, h, w, 3] device tensors (the same frame; any length), mask [h, w] / [B, h, w] bool or uint8.  Per image, over
+    the pixels where the mask is set and both normals have a finite non-zero length (cn_normal_errors): the mean,
+    median and root-mean-square angle in degrees and the share of pixels below 11.25, 22.5 and 30 degrees; the
+    median is taken over the kernel's angle buffer on the device by np.median's rule.  Returns the means of the
+    per-image values over the images that have a valid pixel, or None when none has one."""
+    if pred.dim() == 3:
+        pred, gt, mask = pred[None], gt[None], None if mask is None else mask[None]
+    if pred.dim() != 4 or pred.shape[-1] != 3 or gt.shape != pred.shape or (mask is not None and mask.shape != pred.shape[:3]):
+        raise ValueError(f"normal_metrics: maps [h, w, 3] or [B, h, w, 3] and a mask [h, w] or [B, h, w] (got "
+                         f"{tuple(pred.shape)}, {tuple(gt.shape)}, {None if mask is None else tuple(mask.shape)})")
+    rows = []
+    for b in range(pred.shape[0]):
+        m = None if mask is None else mask[b].reshape(-1).contiguous()
+        angle, sums = ops.normal_errors(pred[b].reshape(-1, 3).float().contiguous(), gt[b].reshape(-1, 3).float().contiguous(), m)
+        s = torch.where(torch.isnan(angle), torch.full((), float("inf"), device=angle.device), angle).sort().values
+        n, tot, sq, c11, c22, c30 = sums.tolist()
+        n = int(n)
+        if n == 0:
+            continue
+        med = (s[(n - 1) // 2].double() + s[n // 2].double()) / 2
+        rows.append([tot / n, float(med), math.sqrt(sq / n), c11 / n, c22 / n, c30 / n])
+    if not rows:
+        return None
+    return dict(zip(NORMAL_KEYS, np.asarray(rows, dtype=np.float64).mean(0).tolist()))
+
+
+# ---------------------------------------------------------------------------
 # pose metrics (host, float64)
 def _np_poses(x):
     if torch.is_tensor(x):
@@ -461,6 +494,27 @@ def _cloud_side(queries, targets, threshold, max_dist, crop_min, crop_max):
     return ops.cloud_stats(dist, threshold, max_dist, queries if crop_min is not None else None, crop_min, crop_max)
 
 
+def _cloud_side_normals(queries, targets, threshold, max_dist, crop_min, crop_max, query_normals, target_normals):
+    """_cloud_side's statistics and cloud_normal_stats of the same pairs, from one nearest-neighbour search."""
+    dist, index = nearest_distances(queries, targets, max_dist)
+    pts = queries if crop_min is not None else None
+    return (ops.cloud_stats(dist, threshold, max_dist, pts, crop_min, crop_max),
+            ops.cloud_normal_stats(query_normals, target_normals, index, dist, max_dist, pts, crop_min, crop_max))
+
+
+NORMAL_GEOMETRY_KEYS = ("normal_accuracy", "normal_completeness", "normal_consistency", "n_pred_normal", "n_gt_normal")
+
+
+def normal_geometry_from_stats(pred, gt):
+    """The normal-consistency entries from the two cn_cloud_normal_stats results (pairs counted, sum of |cos|,
+    pairs left out), mesh samples first."""
+    (cp, sp, _), (cg, sg, _) = pred, gt
+    acc = sp / cp if cp else float("nan")
+    comp = sg / cg if cg else float("nan")
+    return {"normal_accuracy": acc, "normal_completeness": comp, "normal_consistency": 0.5 * (acc + comp),
+            "n_pred_normal": int(cp), "n_gt_normal": int(cg)}
+
+
 def geometry_from_stats(pred, gt, area):
     """The metric dict from the two cn_cloud_stats results (4 numbers each: inside the crop, of those within
     max_dist, the sum of their distances, of those below the threshold), mesh samples first."""
@@ -476,7 +530,8 @@ def geometry_from_stats(pred, gt, area):
 
 def mesh_geometry_metrics(vertices, triangles, gt_points, *, threshold, max_dist=math.inf, n_samples=None,
                           density=None, seed=0, transform=None, crop_min=None, crop_max=None, cull_views=None,
-                          cull_resolution=None, cull_gt=False, cull_min_views=1, cull_tol_abs=None, cull_tol_rel=None):
+                          cull_resolution=None, cull_gt=False, cull_min_views=1, cull_tol_abs=None, cull_tol_rel=None,
+                          gt_normals=None):
     """Geometry metrics of a triangle mesh against a ground-truth cloud, all on the device.  vertices fp32
     [V, 3], triangles int32 [T, 3] (NeuSRenderer.extract_geometry's output as it is) and gt_points fp32 [N, 3]
     are device tensors.  The mesh is sampled uniformly by area (cn_mesh_area / cn_mesh_sample, Philox seed
@@ -495,7 +550,18 @@ def mesh_geometry_metrics(vertices, triangles, gt_points, *, threshold, max_dist
     to what at least cull_min_views of them see (mesh.cull_mesh with cull_tol_abs / cull_tol_rel, by default
     cull_mesh's), before `transform` and before sampling, as the ScanNet / DTU / Tanks-and-Temples protocols do.
     cull_gt drops the ground-truth points outside every view's frustum, the cameras taken through `transform`
-    into the ground truth's frame.  Without them nothing changes."""
+    into the ground truth's frame.  Without them nothing changes.
+    gt_normals fp32 [N, 3] (any length, the ground truth's frame; cull_gt filters them with the points) adds the
+    normal consistency: every mesh sample carries the face normal of the (transformed) triangle it was drawn
+    from, and over the same pairs as the distance means
+      normal_accuracy      mean |n_sample . n_gt[nearest]| from the mesh samples to the ground truth;
+      normal_completeness  the same from the ground truth to the mesh samples;  normal_consistency: their mean;
+      n_pred_normal, n_gt_normal  the pairs counted (pairs with a zero or non-finite normal are left out).
+    Without gt_normals the dict has exactly the keys above."""
+    if gt_normals is not None:
+        ops._need_cloud("mesh_geometry_metrics", gt_normals, "gt_normals")
+        if gt_normals.shape[0] != gt_points.shape[0]:
+            raise ValueError(f"mesh_geometry_metrics: {gt_normals.shape[0]} normals for {gt_points.shape[0]} points")
     if (n_samples is None) == (density is None):
         raise ValueError("mesh_geometry_metrics: exactly one of n_samples and density")
     if (cull_views is None) != (cull_resolution is None):
@@ -518,6 +584,8 @@ def mesh_geometry_metrics(vertices, triangles, gt_points, *, threshold, max_dist
         if cull_gt:
             h, w = (int(x) for x in cull_resolution)
             seen = ops.mesh_visibility(gt_points, mesh.view_projections(cull_views, (h, w), transform, dev), h, w)
+            if gt_normals is not None:
+                gt_normals = gt_normals[seen > 0].contiguous()
             gt_points = gt_points[seen > 0].contiguous()
     if transform is not None:
         M = torch.as_tensor(np.asarray(transform.detach().cpu() if torch.is_tensor(transform) else transform,
@@ -535,11 +603,25 @@ def mesh_geometry_metrics(vertices, triangles, gt_points, *, threshold, max_dist
     if S < 1 or S >= 2 ** 31:
         raise ValueError(f"mesh_geometry_metrics: {S} samples")
     philox = torch.tensor([int(seed), 0], dtype=torch.uint64, device=dev)
-    samples, _ = ops.mesh_sample(handle, S, philox)
-    pred = _cloud_side(samples, gt_points, threshold, max_dist, crop_min, crop_max)
-    gt = _cloud_side(gt_points, samples, threshold, max_dist, crop_min, crop_max)
+    samples, sample_tri = ops.mesh_sample(handle, S, philox, want_tri=gt_normals is not None)
+    sample_normals = None
+    if gt_normals is not None:
+        # the face normals at the samples' triangles (cn_cloud_normal_stats normalises them); a sample without a
+        # triangle (-1) gets the zero normal and is left out
+        corners = vertices[triangles[sample_tri.clamp(min=0).long()].long()]
+        sample_normals = torch.cross(corners[:, 1] - corners[:, 0], corners[:, 2] - corners[:, 0], dim=-1)
+        sample_normals = torch.where((sample_tri >= 0)[:, None], sample_normals, torch.zeros_like(sample_normals)).contiguous()
+    if gt_normals is None:
+        pred = _cloud_side(samples, gt_points, threshold, max_dist, crop_min, crop_max)
+        gt = _cloud_side(gt_points, samples, threshold, max_dist, crop_min, crop_max)
+        both = torch.stack([pred, gt]).tolist()
+        return geometry_from_stats(both[0], both[1], area)
+    pred, pred_n = _cloud_side_normals(samples, gt_points, threshold, max_dist, crop_min, crop_max, sample_normals, gt_normals)
+    gt, gt_n = _cloud_side_normals(gt_points, samples, threshold, max_dist, crop_min, crop_max, gt_normals, sample_normals)
     both = torch.stack([pred, gt]).tolist()
-    return geometry_from_stats(both[0], both[1], area)
+    res = geometry_from_stats(both[0], both[1], area)
+    res.update(normal_geometry_from_stats(*torch.stack([pred_n, gt_n]).tolist()))
+    return res
 
 
 # ---------------------------------------------------------------------------

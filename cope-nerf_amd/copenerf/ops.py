@@ -1465,6 +1465,47 @@ def cloud_stats(dist, threshold, max_dist=math.inf, points=None, crop_min=None, 
     return out
 
 
+def cloud_normal_stats(query_normals, target_normals, index, dist, max_dist=math.inf, points=None, crop_min=None,
+                       crop_max=None):
+    """cn_cloud_normal_stats: a device double [3] = (pairs counted, the sum of |q . t[index]| over them, pairs left
+    out for a zero or non-finite normal) over query_normals fp32 [Q, 3], target_normals fp32 [N, 3] and nn_query's
+    index int32 [Q] / dist fp32 [Q] (with the same max_dist).  A pair is counted when index >= 0, dist < max_dist, the
+    query lies inside the crop box (points with crop_min / crop_max, as cloud_stats) and both normals are usable;
+    both are normalised in the kernel."""
+    _need_cloud("cloud_normal_stats", query_normals, "query_normals")
+    _need_cloud("cloud_normal_stats", target_normals, "target_normals")
+    dev = query_normals.device
+    d = _lib.CloudNormalStatsDesc()
+    d.Q, d.N = query_normals.shape[0], target_normals.shape[0]
+    _need(index, "index", ndim=0)
+    _need(dist, "dist", ndim=0)
+    if index.dtype != torch.int32 or tuple(index.shape) != (d.Q,) or not index.is_contiguous() or \
+            dist.dtype != torch.float32 or tuple(dist.shape) != (d.Q,) or not dist.is_contiguous():
+        raise RuntimeError(f"cloud_normal_stats: index int32 [{d.Q}] and dist fp32 [{d.Q}] contiguous device tensors "
+                           f"(got {index.dtype} {tuple(index.shape)}, {dist.dtype} {tuple(dist.shape)})")
+    if any(t.device != dev for t in (target_normals, index, dist)):
+        raise RuntimeError("cloud_normal_stats: tensors on different devices")
+    if (crop_min is None) != (crop_max is None) or (crop_min is not None and points is None):
+        raise RuntimeError("cloud_normal_stats: a crop box needs crop_min, crop_max and points")
+    if crop_min is not None:
+        _need_cloud("cloud_normal_stats", points, "points")
+        if points.shape[0] != d.Q or points.device != dev:
+            raise RuntimeError(f"cloud_normal_stats: points {tuple(points.shape)} for {d.Q} queries")
+        d.points = _ptr(points) if d.Q else None
+        d.crop_min = (_lib.c_f32 * 3)(*[float(x) for x in crop_min])
+        d.crop_max = (_lib.c_f32 * 3)(*[float(x) for x in crop_max])
+    if d.Q:
+        d.query_normals, d.index, d.dist = _ptr(query_normals), _ptr(index), _ptr(dist)
+    d.target_normals = _ptr(target_normals) if d.N else None
+    d.max_dist = float(max_dist)
+    out = torch.empty(3, dtype=torch.float64, device=dev)
+    d.out = _ptr(out)
+    lib = _lib.load()
+    ws = _workspace(lib.cn_cloud_normal_stats_workspace_bytes(d.Q), dev)
+    _lib.check(lib.cn_cloud_normal_stats(ctypes.byref(d), _ptr(ws), ws.numel(), _stream()), "cn_cloud_normal_stats")
+    return out
+
+
 # ---------------------------------------------------------------------------
 # Mesh depth rendering and visibility (additive to ABI v22): cn_mesh_raster.hip
 MESH_NEAR = 1e-4  # the default near bound on a corner's (or a point's) depth c
@@ -1534,6 +1575,90 @@ def mesh_visibility(points, proj, h, w, depth=None, tol_abs=0.0, tol_rel=0.0, ne
     d.proj = _ptr(proj) if d.N else None
     _lib.call("cn_mesh_visibility", ctypes.byref(d), _stream())
     return count
+
+
+MESH_SHADE_GREY = 0.8  # the albedo of a mesh shaded without colours
+
+
+def mesh_shade(vertices, triangles, proj, tri, *, attr=None, vnormals=None, rot=None, want=("normal",), fill=0.0,
+               light=(0.0, 0.0, 1.0), ambient=0.3, grey=MESH_SHADE_GREY, albedo_from_attr=False, background=(255, 255, 255)):
+    """What mesh_raster's tri int32 [N, h, w] shows -- cn_mesh_shade: a dict with the outputs named in `want`:
+      "attr"          fp32 [N, h, w, C]: attr fp32 [V, C] (1 <= C <= 16) interpolated perspective-correctly, `fill`
+                      where nothing is seen;
+      "normal"        fp32 [N, h, w, 3]: the unit normal turned towards the camera -- the triangle's own, or with
+                      vnormals fp32 [V, 3] the interpolated vertex normal -- rotated by rot fp32 [N, 3, 3] when given;
+                      zero where nothing is seen;
+      "normal_image"  uint8 [N, h, w, 3]: normal * 128 + 128, visualize's picture of a normal map;
+      "shaded"        uint8 [N, h, w, 3]: albedo (ambient + (1 - ambient) max(0, normal . light)) * 255, the albedo
+                      `grey` or, with albedo_from_attr, the first three channels of the interpolated attr ([0, 1]);
+    the pictures show `background` (three uint8) where nothing is seen.  light is used as given (a unit vector in
+    the normals' frame).  One thread per pixel, no atomics: given tri the result is bitwise repeatable."""
+    _need_cloud("mesh_shade", vertices, "vertices")
+    _need_cloud("mesh_shade", triangles, "triangles", dtype=torch.int32)
+    dev = vertices.device
+    if triangles.device != dev:
+        raise RuntimeError("mesh_shade: vertices and triangles on different devices")
+    _need_proj("mesh_shade", proj, dev)
+    _need(tri, "tri", ndim=0)
+    if tri.dtype != torch.int32 or tri.dim() != 3 or tri.shape[0] != proj.shape[0] or not tri.is_contiguous() or tri.device != dev:
+        raise RuntimeError(f"mesh_shade: tri must be a contiguous int32 [{proj.shape[0]}, h, w] tensor on the vertices' "
+                           f"device (got {tri.dtype}, shape {tuple(tri.shape)})")
+    want = tuple(want)
+    unknown = set(want) - {"attr", "normal", "normal_image", "shaded"}
+    if unknown or not want:
+        raise RuntimeError(f"mesh_shade: want {want} (of attr, normal, normal_image, shaded)")
+    d = _lib.MeshShadeDesc()
+    d.V, d.T, d.N, d.h, d.w = vertices.shape[0], triangles.shape[0], tri.shape[0], tri.shape[1], tri.shape[2]
+    if d.h < 1 or d.w < 1:
+        raise RuntimeError(f"mesh_shade: image {d.h} x {d.w}")
+    d.vertices, d.triangles = _ptr(vertices) if d.V else None, _ptr(triangles) if d.T else None
+
+    keep = []  # placeholders that must outlive the call
+
+    def per_vertex(t, name, cols):
+        _need_cloud("mesh_shade", t, name, cols=cols)
+        if t.shape[0] != d.V or t.device != dev:
+            raise RuntimeError(f"mesh_shade: {name} {tuple(t.shape)} for {d.V} vertices")
+        if not d.V:  # (no vertex, so every pixel is background: the library still wants a pointer)
+            keep.append(torch.zeros(1, cols, dtype=torch.float32, device=dev))
+        return _ptr(t) if d.V else _ptr(keep[-1])
+
+    if attr is not None:
+        if attr.dim() != 2 or not 1 <= attr.shape[1] <= 16:
+            raise RuntimeError(f"mesh_shade: attr must be [V, C] with 1 <= C <= 16 (got {tuple(attr.shape)})")
+        d.C = attr.shape[1]
+        d.attr = per_vertex(attr, "attr", d.C)
+    elif "attr" in want or albedo_from_attr:
+        raise RuntimeError("mesh_shade: the attr output and albedo_from_attr need attr")
+    if albedo_from_attr and d.C < 3:
+        raise RuntimeError(f"mesh_shade: albedo_from_attr needs at least 3 channels, attr has {d.C}")
+    if vnormals is not None:
+        d.vnormals = per_vertex(vnormals, "vnormals", 3)
+    if rot is not None:
+        _need(rot, "rot", ndim=0)
+        if rot.dtype != torch.float32 or tuple(rot.shape) != (d.N, 3, 3) or not rot.is_contiguous() or rot.device != dev:
+            raise RuntimeError(f"mesh_shade: rot must be a contiguous fp32 [{d.N}, 3, 3] tensor on the vertices' device "
+                               f"(got {rot.dtype}, shape {tuple(rot.shape)})")
+        d.rot = _ptr(rot) if d.N else None
+    d.fill, d.ambient, d.grey, d.albedo_from_attr = float(fill), float(ambient), float(grey), int(bool(albedo_from_attr))
+    d.light = (_lib.c_f32 * 3)(*[float(x) for x in light])
+    d.background = (ctypes.c_uint8 * 3)(*[int(x) for x in background])
+    out = {}
+    if "attr" in want:
+        out["attr"] = torch.empty(d.N, d.h, d.w, d.C, dtype=torch.float32, device=dev)
+    if "normal" in want:
+        out["normal"] = torch.empty(d.N, d.h, d.w, 3, dtype=torch.float32, device=dev)
+    if "normal_image" in want:
+        out["normal_image"] = torch.empty(d.N, d.h, d.w, 3, dtype=torch.uint8, device=dev)
+    if "shaded" in want:
+        out["shaded"] = torch.empty(d.N, d.h, d.w, 3, dtype=torch.uint8, device=dev)
+    if d.N:
+        d.proj, d.tri = _ptr(proj), _ptr(tri)
+        for key, field in (("attr", "attr_out"), ("normal", "normal_out"), ("normal_image", "normal_img"), ("shaded", "shaded_img")):
+            if key in out:
+                setattr(d, field, _ptr(out[key]))
+    _lib.call("cn_mesh_shade", ctypes.byref(d), _stream())
+    return out
 
 
 # ---------------------------------------------------------------------------
@@ -1729,3 +1854,29 @@ def depth_errors(gt, pred, ratio, min_depth, max_depth, clamp):
               float(min_depth), float(max_depth), int(bool(clamp)), _ptr(out), _ptr(ws), need,
               torch.cuda.current_stream(dev).cuda_stream)
     return out
+
+
+def normal_errors(pred, gt, mask=None):
+    """cn_normal_errors: (angle fp32 [n], sums double [6]) for two normal maps pred, gt fp32 [n, 3] and an optional
+    uint8 / bool mask [n], all contiguous on one device.  angle: the angle between the two normals in degrees,
+    atan2(|p x g|, p . g) of the normalised vectors, NaN where the mask is 0 or a normal has a zero or non-finite
+    length; sums = (valid pixels, sum angle, sum angle^2, count < 11.25, count < 22.5, count < 30 degrees)."""
+    _need_cloud("normal_errors", pred, "pred")
+    _need_cloud("normal_errors", gt, "gt")
+    n, dev = pred.shape[0], pred.device
+    if gt.shape[0] != n or gt.device != dev:
+        raise RuntimeError(f"normal_errors: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} on one device")
+    if mask is not None:
+        if mask.dtype == torch.bool:
+            mask = mask.to(torch.uint8)
+        if not mask.is_cuda or mask.dtype != torch.uint8 or tuple(mask.shape) != (n,) or not mask.is_contiguous() or \
+                mask.device != dev:
+            raise RuntimeError(f"normal_errors: mask must be a contiguous bool or uint8 [{n}] tensor on the maps' device")
+    angle = torch.empty(n, dtype=torch.float32, device=dev)
+    sums = torch.empty(6, dtype=torch.float64, device=dev)
+    lib = _lib.load()
+    ws = _workspace(lib.cn_normal_errors_workspace_bytes(n), dev)
+    _lib.call("cn_normal_errors", n, _ptr(pred) if n else None, _ptr(gt) if n else None,
+              _ptr(mask) if n and mask is not None else None, _ptr(angle) if n else None, _ptr(sums), _ptr(ws), ws.numel(),
+              _stream())
+    return angle, sums

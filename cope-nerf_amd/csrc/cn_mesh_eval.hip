@@ -552,6 +552,77 @@ __global__ void __launch_bounds__(kStatsThreads) stats_final_kernel(int nb, cons
     }
 }
 
+// ---- normal statistics ----------------------------------------------------------------------------------
+
+struct NormalStatsArgs {
+    int64_t Q, N;
+    const float* qn;
+    const float* tn;
+    const int32_t* index;
+    const float* dist;
+    const float* pts;
+    float lo[3], hi[3];
+    float max_dist;
+    double* part;  // [blocks][3]
+    double* out;   // [3]
+};
+
+// v / |v| in fp32, |v| = sqrt((x x + y y) + z z); false for a zero or non-finite length
+__device__ __forceinline__ bool unit3(const float* __restrict__ v, float* o) {
+    const float len = sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+    if (!(len > 0.0f && len < INFINITY)) return false;
+    o[0] = v[0] / len;
+    o[1] = v[1] / len;
+    o[2] = v[2] / len;
+    return true;
+}
+
+// launch 1, laid out as stats_partial_kernel: (pairs counted, the sum of |q . t|, pairs left out for a normal)
+__global__ void __launch_bounds__(kStatsThreads) normal_stats_partial_kernel(NormalStatsArgs a) {
+    __shared__ double sh[kStatsThreads / kWave];
+    const int64_t stride = (int64_t)gridDim.x * kStatsThreads;
+    double v[3] = {0.0, 0.0, 0.0};
+    for (int64_t i = (int64_t)blockIdx.x * kStatsThreads + threadIdx.x; i < a.Q; i += stride) {  // bound: ceil(Q / stride)
+        bool in = true;
+        if (a.pts) {
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                const float p = a.pts[i * 3 + ax];
+                in = in && p >= a.lo[ax] && p <= a.hi[ax];
+            }
+        }
+        const int32_t j = a.index[i];
+        if (!(in && j >= 0 && j < a.N && a.dist[i] < a.max_dist)) continue;  // (an index past the targets reads nothing)
+        float q[3], t[3];
+        if (unit3(a.qn + i * 3, q) && unit3(a.tn + (int64_t)j * 3, t)) {
+            v[0] += 1.0;
+            v[1] = v[1] + (double)fabsf((q[0] * t[0] + q[1] * t[1]) + q[2] * t[2]);
+        } else {
+            v[2] += 1.0;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double s = block_sum_fixed(v[k], sh);
+        if (threadIdx.x == 0) a.part[(int64_t)blockIdx.x * 3 + k] = s;
+    }
+}
+
+// launch 2 (one block): the block partials, thread t takes blocks t, t + 256, ...
+__global__ void __launch_bounds__(kStatsThreads) normal_stats_final_kernel(int nb, const double* __restrict__ part,
+                                                                           double* __restrict__ out) {
+    __shared__ double sh[kStatsThreads / kWave];
+    double v[3] = {0.0, 0.0, 0.0};
+    for (int b = threadIdx.x; b < nb; b += kStatsThreads)  // bound: ceil(nb / 256) <= 4
+#pragma unroll
+        for (int k = 0; k < 3; ++k) v[k] = v[k] + part[(int64_t)b * 3 + k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double s = block_sum_fixed(v[k], sh);
+        if (threadIdx.x == 0) out[k] = s;
+    }
+}
+
 }  // namespace
 }  // namespace cn
 
@@ -699,4 +770,50 @@ extern "C" int cn_cloud_stats(const cn_cloud_stats_desc* d, void* workspace, int
     if (rc) return rc;
     stats_final_kernel<<<1, kStatsThreads, 0, st>>>(nb, a.part, a.out);
     return check_launch("cn_cloud_stats");
+}
+
+extern "C" size_t cn_cloud_normal_stats_workspace_bytes(int64_t Q) {
+    if (Q < 0 || Q > kMaxCount) return 0;
+    return rup_sz((size_t)stats_blocks(Q) * 3 * sizeof(double));
+}
+
+extern "C" int cn_cloud_normal_stats(const cn_cloud_normal_stats_desc* d, void* workspace, int64_t workspace_bytes,
+                                     cn_stream_t stream) {
+    CN_REQUIRE(d, CN_ERR_ARG, "cn_cloud_normal_stats: null descriptor");
+    CN_REQUIRE(d->Q >= 0 && d->Q <= kMaxCount && d->N >= 0 && d->N <= kMaxCount, CN_ERR_SHAPE,
+               "cn_cloud_normal_stats: Q %lld, N %lld (each in [0, 2^31))", (long long)d->Q, (long long)d->N);
+    CN_REQUIRE(!(d->max_dist != d->max_dist), CN_ERR_SHAPE, "cn_cloud_normal_stats: max_dist is NaN");
+    CN_REQUIRE(d->out, CN_ERR_ARG, "cn_cloud_normal_stats: null out");
+    CN_REQUIRE(d->Q == 0 || (d->query_normals && d->index && d->dist), CN_ERR_ARG,
+               "cn_cloud_normal_stats: null query_normals / index / dist");
+    CN_REQUIRE(d->Q == 0 || d->N == 0 || d->target_normals, CN_ERR_ARG, "cn_cloud_normal_stats: null target_normals");
+    CN_REQUIRE((((uintptr_t)d->query_normals | (uintptr_t)d->target_normals | (uintptr_t)d->index | (uintptr_t)d->dist |
+                 (uintptr_t)d->points) & 3) == 0 && ((uintptr_t)d->out & 7) == 0,
+               CN_ERR_ALIGN, "cn_cloud_normal_stats: normals / index / dist / points 4-byte, out 8-byte aligned");
+    const size_t need = cn_cloud_normal_stats_workspace_bytes(d->Q);
+    CN_REQUIRE(workspace && workspace_bytes >= 0 && (size_t)workspace_bytes >= need, CN_ERR_SHAPE,
+               "cn_cloud_normal_stats: workspace %lld bytes, %zu needed", (long long)workspace_bytes, need);
+    CN_REQUIRE(((uintptr_t)workspace & (kAlign - 1)) == 0, CN_ERR_ALIGN, "cn_cloud_normal_stats: workspace not 256-byte aligned");
+    NormalStatsArgs a{};
+    a.Q = d->Q;
+    a.N = d->N;
+    a.qn = d->query_normals;
+    a.tn = d->target_normals;
+    a.index = d->index;
+    a.dist = d->dist;
+    a.pts = d->points;
+    for (int i = 0; i < 3; ++i) {
+        a.lo[i] = d->crop_min[i];
+        a.hi[i] = d->crop_max[i];
+    }
+    a.max_dist = d->max_dist;
+    a.part = static_cast<double*>(workspace);
+    a.out = d->out;
+    hipStream_t st = (hipStream_t)stream;
+    const int nb = stats_blocks(d->Q);
+    normal_stats_partial_kernel<<<nb, kStatsThreads, 0, st>>>(a);
+    int rc = check_launch("cn_cloud_normal_stats");
+    if (rc) return rc;
+    normal_stats_final_kernel<<<1, kStatsThreads, 0, st>>>(nb, a.part, a.out);
+    return check_launch("cn_cloud_normal_stats");
 }

@@ -274,6 +274,86 @@ int depth_shape_check(const char* who, int N, int Hg, int Wg) {
     return CN_OK;
 }
 
+// cn_normal_errors: the angle between two normal maps, per pixel and summed.
+constexpr int kNormalPerBlock = 2048;  // pixels per workgroup
+constexpr int kNormalMaxBlocks = 1024;
+
+int normal_blocks(int64_t n) {
+    int64_t b = (n + kNormalPerBlock - 1) / kNormalPerBlock;
+    return (int)(b < 1 ? 1 : (b > kNormalMaxBlocks ? kNormalMaxBlocks : b));
+}
+
+struct NormalArgs {
+    int64_t n;
+    const float* pred;
+    const float* gt;
+    const uint8_t* mask;
+    float* angle;
+    double* part;  // [blocks][6]
+};
+
+__device__ __forceinline__ bool unit3(const float* __restrict__ v, float* o) {
+    const float len = sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+    if (!(len > 0.0f && len < INFINITY)) return false;
+    o[0] = v[0] / len;
+    o[1] = v[1] / len;
+    o[2] = v[2] / len;
+    return true;
+}
+
+// the sum over the block of one double per thread in a fixed tree (lanes by shuffles, then the four waves in order)
+__device__ __forceinline__ double block_sum_d(double x, double* sh) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x = x + __shfl_down(x, o, 64);
+    __syncthreads();  // (a previous call's readers are done)
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
+    __syncthreads();
+    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+
+// thread t of block b takes pixels (b 256 + t) + j (blocks 256), j ascending: angle = atan2(|p x g|, p . g) of the
+// normalised vectors in fp32, in degrees (the radians scaled in double, rounded once); the six sums in double.
+__global__ void __launch_bounds__(256) normal_errors_kernel(NormalArgs a) {
+    __shared__ double sh[4];
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    double s[6] = {};
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n; i += stride) {  // bound: ceil(n / stride)
+        float p[3], g[3], ang = NAN;
+        if ((!a.mask || a.mask[i]) && unit3(a.pred + i * 3, p) && unit3(a.gt + i * 3, g)) {
+            const float cx = p[1] * g[2] - p[2] * g[1], cy = p[2] * g[0] - p[0] * g[2], cz = p[0] * g[1] - p[1] * g[0];
+            const float cr = sqrtf((cx * cx + cy * cy) + cz * cz);
+            const float dt = (p[0] * g[0] + p[1] * g[1]) + p[2] * g[2];
+            ang = (float)((double)atan2f(cr, dt) * 57.29577951308232);
+            s[0] += 1.0;
+            s[1] = s[1] + (double)ang;
+            s[2] = s[2] + (double)ang * (double)ang;
+            s[3] += ang < 11.25f ? 1.0 : 0.0;
+            s[4] += ang < 22.5f ? 1.0 : 0.0;
+            s[5] += ang < 30.0f ? 1.0 : 0.0;
+        }
+        a.angle[i] = ang;
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const double r = block_sum_d(s[k], sh);
+        if (threadIdx.x == 0) a.part[(int64_t)blockIdx.x * 6 + k] = r;
+    }
+}
+
+// one block: the block partials, thread t takes blocks t, t + 256, ...
+__global__ void __launch_bounds__(256) normal_reduce_kernel(int nb, const double* __restrict__ part, double* __restrict__ out) {
+    __shared__ double sh[4];
+    double s[6] = {};
+    for (int b = threadIdx.x; b < nb; b += 256)  // bound: ceil(nb / 256) <= 4
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s[k] = s[k] + part[(int64_t)b * 6 + k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const double r = block_sum_d(s[k], sh);
+        if (threadIdx.x == 0) out[k] = r;
+    }
+}
+
 size_t round_up(size_t b) { return (b + kAlign - 1) / kAlign * kAlign; }
 
 }  // namespace
@@ -337,4 +417,28 @@ extern "C" int cn_depth_errors(int32_t N, int32_t Hg, int32_t Wg, const float* g
     if (int rc = check_launch("cn_depth_errors")) return rc;
     depth_reduce_kernel<<<dim3((unsigned)N), 64, 0, st>>>(a.part, blocks, out);
     return check_launch("cn_depth_errors (reduce)");
+}
+
+extern "C" size_t cn_normal_errors_workspace_bytes(int64_t n) {
+    if (n < 0 || n >= ((int64_t)1 << 31)) return 0;
+    return round_up((size_t)normal_blocks(n) * 6 * sizeof(double));
+}
+
+extern "C" int cn_normal_errors(int64_t n, const float* pred, const float* gt, const uint8_t* mask, float* angle, double* out,
+                                void* workspace, int64_t workspace_bytes, cn_stream_t stream) {
+    CN_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), CN_ERR_SHAPE, "cn_normal_errors: n %lld (in [0, 2^31))", (long long)n);
+    CN_REQUIRE(out && (n == 0 || (pred && gt && angle)), CN_ERR_ARG, "cn_normal_errors: null pred / gt / angle / out");
+    CN_REQUIRE((((uintptr_t)pred | (uintptr_t)gt | (uintptr_t)angle) & 3) == 0 && ((uintptr_t)out & 7) == 0, CN_ERR_ALIGN,
+               "cn_normal_errors: pred / gt / angle 4-byte, out 8-byte aligned");
+    const size_t need = cn_normal_errors_workspace_bytes(n);
+    CN_REQUIRE(workspace && workspace_bytes >= 0 && (size_t)workspace_bytes >= need, CN_ERR_SHAPE,
+               "cn_normal_errors: workspace %lld bytes, %zu needed", (long long)workspace_bytes, need);
+    CN_REQUIRE(((uintptr_t)workspace & (kAlign - 1)) == 0, CN_ERR_ALIGN, "cn_normal_errors: workspace not 256-byte aligned");
+    const int nb = normal_blocks(n);
+    hipStream_t st = (hipStream_t)stream;
+    NormalArgs a{n, pred, gt, mask, angle, static_cast<double*>(workspace)};
+    normal_errors_kernel<<<nb, 256, 0, st>>>(a);
+    if (int rc = check_launch("cn_normal_errors")) return rc;
+    normal_reduce_kernel<<<1, 256, 0, st>>>(nb, a.part, out);
+    return check_launch("cn_normal_errors (reduce)");
 }

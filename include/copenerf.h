@@ -1065,6 +1065,31 @@ typedef struct cn_cloud_stats_desc {
 size_t cn_cloud_stats_workspace_bytes(int64_t Q);
 int cn_cloud_stats(const cn_cloud_stats_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
 
+/* cn_cloud_normal_stats: the normal-consistency sums of one direction.  Over Q queries with
+ * query_normals [Q][3], cn_nn_query's index / dist [Q] into N targets with target_normals
+ * [N][3]: out (DEVICE double [3]) = (0) the pairs counted, (1) the sum of |q . t[index]| over
+ * them, (2) the pairs left out because a normal has a zero or non-finite length.  A pair is
+ * counted when the query is inside the crop box (cn_cloud_stats' rule; points NULL: no crop),
+ * 0 <= index < N, dist < max_dist and both normals are usable -- the population of
+ * cn_cloud_stats' distance mean.  Both normals are normalised in fp32 (v / sqrt((x x + y y) +
+ * z z)); the dot product is taken in absolute value (orientation is a convention).  The
+ * reduction is cn_cloud_stats' (the same blocks, fixed order, double): bitwise repeatable.
+ * Workspace (256-byte aligned): 24 blocks, rounded up to 256 bytes. */
+typedef struct cn_cloud_normal_stats_desc {
+    int64_t Q, N;
+    const float* query_normals;         /* [Q][3] */
+    const float* target_normals;        /* [N][3] */
+    const int32_t* index;               /* [Q] */
+    const float* dist;                  /* [Q] */
+    const float* points;                /* [Q][3], or NULL: no crop */
+    float crop_min[3];
+    float crop_max[3];
+    float max_dist;
+    double* out;                        /* device [3] */
+} cn_cloud_normal_stats_desc;
+size_t cn_cloud_normal_stats_workspace_bytes(int64_t Q);
+int cn_cloud_normal_stats(const cn_cloud_normal_stats_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+
 /* ------------------------------------------------------------------------ *
  * Mesh depth rendering and visibility (additive to ABI v22): what the ScanNet / DTU /
  * Tanks-and-Temples protocols cull a predicted mesh with before they measure it.  The
@@ -1126,6 +1151,52 @@ typedef struct cn_mesh_visibility_desc {
     int32_t* count;                     /* [Q] */
 } cn_mesh_visibility_desc;
 int cn_mesh_visibility(const cn_mesh_visibility_desc* d, cn_stream_t stream);
+
+/* cn_mesh_shade: what cn_mesh_raster's tri [N][h][w] shows, one thread per pixel, no atomics,
+ * bitwise repeatable; it takes the rasteriser's tri image and decides no coverage itself.  For
+ * a pixel whose tri is t the three corners are projected and the edge values e_k formed
+ * exactly as cn_mesh_raster documents (the same fp32 operation order), and the
+ * perspective-correct weights are lambda_k = e_k iw_k / ((e_0 iw_0 + e_1 iw_1) + e_2 iw_2).
+ * Outputs, each optional (NULL):
+ *   attr_out [N][h][w][C] = (lambda_0 A_0 + lambda_1 A_1) + lambda_2 A_2 of attr [V][C], 1 <= C <= 16;
+ *   normal_out [N][h][w][3]: the unit geometric normal (X_1 - X_0) x (X_2 - X_0), turned
+ *     towards the camera (two-sided rendering): as wound it faces the camera iff (signed
+ *     screen area of the projected corners) x det(proj[:, :3]) < 0.  With vnormals [V][3]:
+ *     the normalised interpolation of the vertex normals, negated into the oriented face
+ *     normal's hemisphere; a zero or non-finite interpolation leaves the face normal.  With
+ *     rot [N][3][3]: rot[view] . n (e.g. the world-to-camera rotation);
+ *   normal_img uint8 [N][h][w][3] = to_u8(n 128 + 128), cn_visual_images' rule (NaN and
+ *     negatives 0, truncation, saturation at 255);
+ *   shaded_img uint8 [N][h][w][3] = to_u8(albedo (ambient + (1 - ambient) max(0, n . light))
+ *     255), albedo the first three channels of the interpolated attributes with
+ *     albedo_from_attr (C >= 3; colours in [0, 1]), else grey; light: a unit vector in
+ *     normal_out's frame (HOST values).
+ * Background -- tri outside [0, T) or a corner index outside [0, V): fill in attr_out, the zero
+ * vector in normal_out, background in both pictures; nothing else is read for such a pixel.
+ * V, T, h w < 2^31; no workspace. */
+typedef struct cn_mesh_shade_desc {
+    int64_t V, T;
+    const float* vertices;              /* [V][3] */
+    const int32_t* triangles;           /* [T][3] */
+    int32_t N, h, w;
+    int32_t C;                          /* 1 .. 16 with attr */
+    const float* proj;                  /* [N][3][4] */
+    const int32_t* tri;                 /* [N][h][w], cn_mesh_raster's */
+    const float* attr;                  /* [V][C], or NULL */
+    const float* vnormals;              /* [V][3], or NULL: face normals */
+    const float* rot;                   /* [N][3][3], or NULL */
+    float fill;
+    float ambient;                      /* in [0, 1] */
+    float light[3];
+    float grey;
+    int32_t albedo_from_attr;
+    uint8_t background[3];
+    float* attr_out;                    /* [N][h][w][C], or NULL */
+    float* normal_out;                  /* [N][h][w][3], or NULL */
+    uint8_t* normal_img;                /* [N][h][w][3], or NULL */
+    uint8_t* shaded_img;                /* [N][h][w][3], or NULL */
+} cn_mesh_shade_desc;
+int cn_mesh_shade(const cn_mesh_shade_desc* d, cn_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
  * Pose refinement (ABI v17): compute_loss_and_warp_image
@@ -1221,6 +1292,23 @@ size_t cn_depth_errors_workspace_bytes(int32_t N, int32_t Hg, int32_t Wg);
 int cn_depth_errors(int32_t N, int32_t Hg, int32_t Wg, const float* gt, int32_t Hp, int32_t Wp,
                     const float* pred, const float* ratio, float min_depth, float max_depth, int32_t clamp,
                     float* out, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+
+/* cn_normal_errors (additive to ABI v22): the angle between two normal maps pred, gt fp32
+ * [n][3] (any frame, the same for both; any length).  Pixel i is valid when mask (uint8 [n], or
+ * NULL: all) is not 0 and both normals have a finite, non-zero length.  Both are normalised
+ * in fp32 (v / sqrt((x x + y y) + z z)) and
+ *   angle[i] = atan2(|p x g|, p . g) in degrees (fp32; NaN where invalid),
+ * not acos of the dot product, which loses half its digits near 0 degrees.  Identical maps
+ * give 0 exactly, antiparallel ones 180.
+ *   out (DEVICE double [6]) = valid pixels, sum angle, sum angle^2, and the counts of
+ *   angle < 11.25, < 22.5, < 30 degrees.
+ * Fixed-order double reduction (thread t of block b takes pixels b 256 + t + j 256 blocks, a
+ * fixed tree per block, one block over the block partials): bitwise repeatable.  blocks =
+ * min(1024, max(1, ceil(n / 2048))).  n = 0: six zeros.  n < 0 or n >= 2^31: CN_ERR_SHAPE.
+ * Workspace (256-byte aligned): 48 blocks, rounded up to 256 bytes. */
+size_t cn_normal_errors_workspace_bytes(int64_t n);
+int cn_normal_errors(int64_t n, const float* pred, const float* gt, const uint8_t* mask, float* angle, double* out,
+                     void* workspace, int64_t workspace_bytes, cn_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
  * Visualisation renders (ABI v19): Trainer.render_visdata (model/training.py:157-374).

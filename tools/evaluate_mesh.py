@@ -4,7 +4,8 @@ precision / recall / F-score at a threshold in the Tanks and Temples style (metr
     python tools/evaluate_mesh.py MESH.ply GT.ply --threshold T [--max-dist D] (--samples S | --density RHO)
         [--seed N] [--crop-min X Y Z --crop-max X Y Z] [--transform T.npy | --align-poses PRED.npy GT.npy]
         [--cull-views K.npy W2C.npy [SCALE.npy] --cull-resolution H W [--cull-min-views N] [--cull-tol-abs A]
-         [--cull-tol-rel R] [--cull-gt]] [--depths-out DIR] [--culled-out MESH.ply] [--out results.txt]
+         [--cull-tol-rel R] [--cull-gt]] [--depths-out DIR] [--normal-maps-out DIR] [--culled-out MESH.ply]
+        [--normals] [--gt-mesh-samples S] [--out results.txt]
 
 MESH.ply is a triangle mesh (tools/extract_mesh.py's output as it is), GT.ply a point cloud (a mesh's vertices are
 taken as the cloud).  --transform is a 4 x 4 similarity applied to the mesh first.  --align-poses takes two
@@ -16,8 +17,12 @@ world-to-camera matrices [N, 4, 4] and optionally scale matrices [N, 4, 4] or [4
 images of --cull-resolution; --cull-gt also drops the ground-truth points outside every frustum.  --depths-out
 writes the mesh's depth from every view as DIR/depth_%06d.npz (key `pred`, 0 where nothing is seen: what
 pose_refine.load_depth_dir reads and metrics.depth_metrics scores against sensor depth), --culled-out the culled
-mesh.  Prints one `name: value` line per metric and with --out writes them in
-metrics.write_results' format."""
+mesh, --normal-maps-out the mesh's camera-frame normal map from every view as DIR/%06d_normal.png
+(mesh.render_mesh: the picture tools/render_views.py writes for the model).  --normals adds the normal consistency
+(normal_accuracy, normal_completeness, normal_consistency, n_pred_normal, n_gt_normal, after the other entries)
+against GT.ply's normals; the file must hold them.  --gt-mesh-samples S: GT.ply is a mesh; S points drawn uniformly
+by area on it (seed + 1) and their face normals are the ground-truth cloud.  Prints one `name: value` line per
+metric and with --out writes them in metrics.write_results' format."""
 import argparse
 import os
 import sys
@@ -60,7 +65,33 @@ def load_views(paths):
     return views
 
 
-def main(argv=None):
+def load_ground_truth(path, normals=False, mesh_samples=None):
+    """(points, triangles or None, normals or None) of the ground-truth PLY.  With normals and no mesh sampling the
+    file must hold vertex normals; with mesh_samples it must hold faces (the normals are then the faces' own)."""
+    from copenerf.mesh import read_ply
+    points, triangles, nrm, _ = read_ply(path)
+    if mesh_samples is not None:
+        if triangles is None or len(triangles) == 0:
+            raise SystemExit(f"evaluate_mesh: --gt-mesh-samples needs a mesh, {path} has no faces")
+        return points, triangles, None
+    if normals and nrm is None:
+        raise SystemExit(f"evaluate_mesh: --normals needs vertex normals (nx ny nz), {path} has none")
+    return points, None, nrm if normals else None
+
+
+def sample_ground_truth(points, triangles, S, seed, device):
+    """S points uniformly by area on the ground-truth mesh and the normals of the triangles they lie on."""
+    from copenerf import ops
+    v, f = torch.from_numpy(points).to(device), torch.from_numpy(triangles).to(device)
+    handle, _ = ops.mesh_area(v, f)
+    philox = torch.tensor([int(seed), 0], dtype=torch.uint64, device=device)
+    pts, tri = ops.mesh_sample(handle, int(S), philox, want_tri=True)
+    c = v[f[tri.clamp(min=0).long()].long()]
+    n = torch.cross(c[:, 1] - c[:, 0], c[:, 2] - c[:, 0], dim=-1)
+    return pts, torch.where((tri >= 0)[:, None], n, torch.zeros_like(n)).contiguous()
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("mesh")
     ap.add_argument("gt")
@@ -82,6 +113,9 @@ def main(argv=None):
     ap.add_argument("--cull-tol-rel", type=float)
     ap.add_argument("--cull-gt", action="store_true")
     ap.add_argument("--depths-out")
+    ap.add_argument("--normal-maps-out")
+    ap.add_argument("--normals", action="store_true")
+    ap.add_argument("--gt-mesh-samples", type=int)
     ap.add_argument("--culled-out")
     ap.add_argument("--out")
     a = ap.parse_args(argv)
@@ -91,6 +125,15 @@ def main(argv=None):
         ap.error("--cull-views and --cull-resolution go together")
     if a.cull_views is None and (a.cull_gt or a.depths_out or a.culled_out):
         ap.error("--cull-gt, --depths-out and --culled-out need --cull-views")
+    if a.cull_views is None and a.normal_maps_out:
+        ap.error("--normal-maps-out needs --cull-views")
+    if a.gt_mesh_samples is not None and a.gt_mesh_samples < 1:
+        ap.error("--gt-mesh-samples takes a positive count")
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("evaluate_mesh: needs a HIP device; the metrics have no CPU path")
     from copenerf import metrics
@@ -98,7 +141,7 @@ def main(argv=None):
     vertices, triangles, _, _ = read_ply(a.mesh)
     if triangles is None:
         raise SystemExit(f"evaluate_mesh: {a.mesh} has no faces")
-    gt = read_ply(a.gt)[0]
+    gt, gt_triangles, gt_normals = load_ground_truth(a.gt, a.normals, a.gt_mesh_samples)
     transform = None
     if a.transform:
         transform = np.load(a.transform)
@@ -119,11 +162,25 @@ def main(argv=None):
             depth = torch.where(torch.isinf(depth), torch.zeros_like(depth), depth).cpu().numpy()
             for i, d in enumerate(depth):
                 np.savez(os.path.join(a.depths_out, "depth_%06d.npz" % i), pred=d)
+        if a.normal_maps_out:
+            from PIL import Image
+            os.makedirs(a.normal_maps_out, exist_ok=True)
+            pictures = mesh.render_mesh(tv, tf, views, a.cull_resolution)["normal_image"].cpu().numpy()
+            for i, img in enumerate(pictures):
+                Image.fromarray(img).save(os.path.join(a.normal_maps_out, "%06d_normal.png" % i))
         if a.culled_out:
             cv, cf, _ = mesh.cull_mesh(tv, tf, views, a.cull_resolution, min_views=a.cull_min_views, **tol)
             mesh.write_ply(a.culled_out, cv.cpu().numpy(), cf.cpu().numpy())
+    gt_points = torch.from_numpy(gt).to(dev)
+    if a.gt_mesh_samples is not None:
+        gt_points, sampled_normals = sample_ground_truth(gt, gt_triangles, a.gt_mesh_samples, a.seed + 1, dev)
+        gt_normals = sampled_normals if a.normals else None
+    elif gt_normals is not None:
+        gt_normals = torch.from_numpy(np.ascontiguousarray(gt_normals)).to(dev)
+    if gt_normals is not None:
+        cull["gt_normals"] = gt_normals
     result = metrics.mesh_geometry_metrics(
-        tv, tf, torch.from_numpy(gt).to(dev), threshold=a.threshold, max_dist=a.max_dist, n_samples=a.samples,
+        tv, tf, gt_points, threshold=a.threshold, max_dist=a.max_dist, n_samples=a.samples,
         density=a.density, seed=a.seed, transform=transform, crop_min=a.crop_min, crop_max=a.crop_max, **cull)
     for key, value in result.items():
         print(f"{key}: {value}")
