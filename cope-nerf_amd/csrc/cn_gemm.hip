@@ -250,8 +250,14 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC * WM * WN / 4) linear_kernel
         if (what == 1) return;
         // MODE 2: chunk kc of the image is [ldb rows][48 bf16]; the tile's BN rows are 96 * BN contiguous bytes
         const int64_t bofs = MODE == 2 ? ((int64_t)kc * (BK / 16) * p.ldb + n0) * 96 : (int64_t)n0 * p.ldb * ESZB;
+        // (MODE 2: the image's rows under the tile -- a 256-wide tile's last column tile over a 128-padded image,
+        // N = 320 on 384 rows, ends 128 rows before the tile does: the view of the K loop's last chunk must not
+        // reach past the image; rows >= ldb of an earlier chunk read the next chunk, columns >= N either way.
+        // The 64x128-wave tiles span every column with one tile, N <= 256 <= ldb: nothing to clip)
+        constexpr bool kClipB = MODE == 2 && BN > 128 && TM * TN < 8;
+        const int brows = kClipB ? min(BN, p.ldb - n0) : BN;
         const rsrc_t rB = make_view(reinterpret_cast<const float*>(reinterpret_cast<const char*>(cB) + bofs),
-                                    valid ? (MODE == 2 ? ((BK / 16 - 1) * p.ldb + BN) * 96 : BN * p.ldb * ESZB) : 0);
+                                    valid ? (MODE == 2 ? ((BK / 16 - 1) * p.ldb + brows) * 96 : BN * p.ldb * ESZB) : 0);
 #pragma unroll
         for (int q = 0; q < BLD; ++q) rb[kRot ? 0 : set][q] = bload4(rB, voB[q], MODE == 2 ? 0 : k0 * ESZB);
     };

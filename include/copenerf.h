@@ -66,7 +66,8 @@ typedef enum cn_epilogue {
     CN_EPI_STORE = 0,        /* out0 = v + bias                                      */
     CN_EPI_SOFTPLUS = 1,     /* z = v + bias; out0 = softplus_beta(z)/odiv           */
     CN_EPI_RELU = 2,         /* out0 = relu(v + bias)                                */
-    CN_EPI_MUL = 3,          /* out0 = v * sg(aux0) (cols < nsplit); out_split = v (cols >= nsplit) */
+    CN_EPI_MUL = 3,          /* out0 = v * sg(aux0) (cols < nsplit); out_split = v (cols >= nsplit; the raw
+                                product: the split columns take no rank-1 term) */
     CN_EPI_TANGENT = 4,      /* out0 = v * sg(aux0) / odiv                           */
     CN_EPI_BWD_SOFTPLUS = 5, /* out0 = v*sg(aux0) + aux1*aux2*aux2_scale*(1-sg)/sg (0 where sg = 0;
                                 aux1, aux2 both NULL or both set): with aux1 = s (the ∇-pass
@@ -226,7 +227,8 @@ typedef struct cn_wgrad_desc {
     int32_t M, N, K;     /* N, K: valid columns of Y and X (Y/X readable up to the padded tile) */
     int32_t npairs;
     int32_t n_out, k_out;
-    int32_t accumulate;  /* 1: dW += result (db too), 0: dW = result */
+    int32_t accumulate;  /* 1: dW += result (db too), 0: dW = result; M = 0 is an empty sum: dW = db = 0,
+                            or both unchanged when accumulating */
     int32_t mfma_dtype;  /* CN_MFMA_F32, or CN_MFMA_BF16: Y and X rounded to bf16 (RNE) on load,
                             v_mfma_f32_32x32x16_bf16, fp32 accumulation and slab reduction;
                             db is summed from the fp32 values either way;
