@@ -235,6 +235,28 @@ class MeshShadeDesc(ctypes.Structure):
     ]
 
 
+class TsdfDesc(ctypes.Structure):
+    _fields_ = [
+        ("nx", c_i32), ("ny", c_i32), ("nz", c_i32), ("lo", c_f32 * 3), ("hi", c_f32 * 3), ("N", c_i32), ("h", c_i32),
+        ("w", c_i32), ("proj", c_ptr), ("depth", c_ptr), ("color", c_ptr), ("trunc", c_f32), ("near", c_f32),
+        ("depth_max", c_f32), ("no_reject", c_i32), ("tsum", c_ptr), ("wsum", c_ptr), ("csum", c_ptr),
+    ]
+
+
+class TsdfFinalizeDesc(ctypes.Structure):
+    _fields_ = [
+        ("nx", c_i32), ("ny", c_i32), ("nz", c_i32), ("min_weight", c_f32), ("tsum", c_ptr), ("wsum", c_ptr),
+        ("csum", c_ptr), ("u", c_ptr), ("rgb", c_ptr),
+    ]
+
+
+class VolumeSampleDesc(ctypes.Structure):
+    _fields_ = [
+        ("nx", c_i32), ("ny", c_i32), ("nz", c_i32), ("C", c_i32), ("lo", c_f32 * 3), ("hi", c_f32 * 3), ("attr", c_ptr),
+        ("mask", c_ptr), ("Q", c_i64), ("points", c_ptr), ("fill", c_f32), ("out", c_ptr),
+    ]
+
+
 class CloudNormalStatsDesc(ctypes.Structure):
     _fields_ = [
         ("Q", c_i64), ("N", c_i64), ("query_normals", c_ptr), ("target_normals", c_ptr), ("index", c_ptr), ("dist", c_ptr),
@@ -360,6 +382,11 @@ SIGNATURES = {
     "cn_mesh_raster": (c_i32, [ctypes.POINTER(MeshRasterDesc), c_ptr, c_i64, c_ptr]),
     "cn_mesh_visibility": (c_i32, [ctypes.POINTER(MeshVisibilityDesc), c_ptr]),
     "cn_mesh_shade": (c_i32, [ctypes.POINTER(MeshShadeDesc), c_ptr]),
+    "cn_mesh_count_observed": (c_i32, [ctypes.POINTER(MeshDesc), c_ptr, c_i64, c_ptr]),
+    "cn_mesh_emit_observed": (c_i32, [ctypes.POINTER(MeshDesc), c_ptr, c_i64, c_ptr]),
+    "cn_tsdf_integrate": (c_i32, [ctypes.POINTER(TsdfDesc), c_ptr]),
+    "cn_tsdf_finalize": (c_i32, [ctypes.POINTER(TsdfFinalizeDesc), c_ptr]),
+    "cn_volume_sample": (c_i32, [ctypes.POINTER(VolumeSampleDesc), c_ptr]),
     "cn_refine_workspace_bytes":(ctypes.c_size_t, [c_i32, c_i32, c_i32]),
     "cn_refine_warp": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
                                c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),

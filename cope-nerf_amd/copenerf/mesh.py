@@ -2,8 +2,9 @@
 meshes through trimesh, which this package does not depend on) and the reader the geometry metrics load
 meshes and ground-truth clouds with; and what turns a mesh back into per-view depth: camera_projection (the
 project's camera convention as one 3 x 4 matrix), render_mesh_depth and cull_mesh (the view-based cull of the
-ScanNet / DTU / Tanks-and-Temples protocols) over ops.mesh_raster / mesh_visibility / mesh_cull, and render_mesh
-(normal maps, vertex attributes and shaded pictures over ops.mesh_shade)."""
+ScanNet / DTU / Tanks-and-Temples protocols) over ops.mesh_raster / mesh_visibility / mesh_cull, render_mesh
+(normal maps, vertex attributes and shaded pictures over ops.mesh_shade), and fuse_depths, the way back from
+per-view depth to a mesh (fusion.TSDFVolume)."""
 from __future__ import annotations
 
 import numpy as np
@@ -305,3 +306,25 @@ def render_mesh(vertices, triangles, views, resolution, *, normals=None, colors=
         out["attr"] = ops.mesh_shade(vertices, triangles, proj, tri, attr=attrs, want=("attr",))["attr"]
     out["depth"], out["tri"] = depth, tri
     return out
+
+
+# ---------------------------------------------------------------------------
+# depth maps back into a mesh (fusion.TSDFVolume)
+def fuse_depths(depths, views, bound_min, bound_max, dims, trunc=None, *, colors=None, resolution=None, depth_max=None,
+                near=None, transform=None, min_weight=1, keep_largest=False, min_triangles=0, device="cuda",
+                views_per_call=None, stats=None):
+    """Depth maps to a mesh in one call, on the device: fusion.TSDFVolume(...).integrate(...).extract_mesh(...) --
+    depths [N, h, w] (render_image's depth, or a sensor's, 0 / +inf / NaN where nothing is seen) from `views` (the
+    dicts view_projections takes) fused into a dims grid over bound_min .. bound_max and meshed where at least
+    min_weight views observed it.  trunc defaults to four voxels (of the coarsest axis).  Returns numpy (vertices,
+    triangles) and, with colors [N, h, w, 3], the vertex colours uint8 [V, 3]."""
+    dims = (dims,) * 3 if np.isscalar(dims) else tuple(int(n) for n in dims)
+    if trunc is None:
+        lo, hi = np.asarray(bound_min, dtype=np.float64), np.asarray(bound_max, dtype=np.float64)
+        trunc = 4.0 * float(np.max((hi - lo) / (np.asarray(dims) - 1)))
+    from .fusion import TSDFVolume, VIEWS_PER_CALL
+    vol = TSDFVolume(bound_min, bound_max, dims, trunc, device, with_colors=colors is not None)
+    vol.integrate(depths, views, resolution=resolution, colors=colors, depth_max=depth_max, near=near,
+                  transform=transform, views_per_call=views_per_call or VIEWS_PER_CALL)
+    return vol.extract_mesh(min_weight=min_weight, keep_largest=keep_largest, min_triangles=min_triangles,
+                            with_colors=colors is not None, stats=stats)

@@ -1080,21 +1080,24 @@ def _mesh_desc(u, threshold, lo, hi, counts):
     return d
 
 
-def mesh_count(u, threshold, lo, hi):
+def mesh_count(u, threshold, lo, hi, observed=False):
     """The count pass of isosurface -- cn_mesh_count: (descriptor, workspace, counts) with counts a device
-    int64 [2] = (vertices, triangles); the workspace keeps the edge masks and offsets mesh_emit reads."""
+    int64 [2] = (vertices, triangles); the workspace keeps the edge masks and offsets mesh_emit reads.
+    observed: cn_mesh_count_observed -- NaN in u means unobserved (pass the same flag to mesh_emit)."""
     counts = torch.empty(2, dtype=torch.int64, device=u.device if u.is_cuda else None)
     d = _mesh_desc(u, threshold, lo, hi, counts)
     lib = _lib.load()
     ws = torch.empty(max(int(lib.cn_mesh_workspace_bytes(d.nx, d.ny, d.nz)), 1), dtype=torch.uint8, device=u.device)
-    _lib.check(lib.cn_mesh_count(ctypes.byref(d), _ptr(ws), ws.numel(), _stream()), "cn_mesh_count")
+    fn = "cn_mesh_count_observed" if observed else "cn_mesh_count"
+    _lib.check(getattr(lib, fn)(ctypes.byref(d), _ptr(ws), ws.numel(), _stream()), fn)
     return d, ws, counts
 
 
-def mesh_emit(d, ws, vertices, triangles, counts=None):
-    """The emit pass -- cn_mesh_emit into vertices fp32 [V, 3] / triangles int32 [T, 3] with mesh_count's
-    descriptor and workspace.  counts: the (V, T) read back from mesh_count, checked here against the
-    buffers (the kernel checks the device counts again and writes nothing into buffers that are too small)."""
+def mesh_emit(d, ws, vertices, triangles, counts=None, observed=False):
+    """The emit pass -- cn_mesh_emit (observed: cn_mesh_emit_observed) into vertices fp32 [V, 3] / triangles int32
+    [T, 3] with mesh_count's descriptor and workspace.  counts: the (V, T) read back from mesh_count, checked here
+    against the buffers (the kernel checks the device counts again and writes nothing into buffers that are too
+    small)."""
     _need(vertices, "vertices")
     _need(triangles, "triangles")
     if (vertices.dtype != torch.float32 or triangles.dtype != torch.int32 or not vertices.is_contiguous() or
@@ -1105,20 +1108,23 @@ def mesh_emit(d, ws, vertices, triangles, counts=None):
                            f"for counts {tuple(counts)}")
     d.vertices, d.max_vertices = _ptr(vertices) if vertices.shape[0] else None, vertices.shape[0]
     d.triangles, d.max_triangles = _ptr(triangles) if triangles.shape[0] else None, triangles.shape[0]
-    _lib.call("cn_mesh_emit", ctypes.byref(d), _ptr(ws), ws.numel(), _stream())
+    _lib.call("cn_mesh_emit_observed" if observed else "cn_mesh_emit", ctypes.byref(d), _ptr(ws), ws.numel(), _stream())
 
 
-def isosurface(u, threshold, lo, hi):
+def isosurface(u, threshold, lo, hi, observed=False):
     """The isosurface u = threshold of a device volume u [nx, ny, nz] over the box lo .. hi as a welded triangle
     mesh: (vertices fp32 [V, 3], triangles int32 [T, 3]), device tensors ((0, 3) when empty).  Marching
     tetrahedra on the Kuhn split; vertex and triangle order are fixed by the grid (include/copenerf.h), triangle
-    normals point toward larger u.  Count pass, one 16-byte read-back, an exact allocation, emit pass."""
-    d, ws, counts = mesh_count(u, threshold, lo, hi)
+    normals point toward larger u.  Count pass, one 16-byte read-back, an exact allocation, emit pass.
+    observed: NaN in u means unobserved (tsdf_finalize's volume) -- an edge carries a vertex only between two
+    observed ends, a cell emits triangles only when its eight corners are observed; vertices on edges whose every
+    cell was skipped remain, unreferenced (mesh_clean with min_triangles >= 1 removes them)."""
+    d, ws, counts = mesh_count(u, threshold, lo, hi, observed)
     V, T = (int(c) for c in counts.tolist())
     vertices = torch.empty(V, 3, device=u.device)
     triangles = torch.empty(T, 3, dtype=torch.int32, device=u.device)
     if V or T:
-        mesh_emit(d, ws, vertices, triangles, (V, T))
+        mesh_emit(d, ws, vertices, triangles, (V, T), observed)
     return vertices, triangles
 
 
@@ -1575,6 +1581,98 @@ def mesh_visibility(points, proj, h, w, depth=None, tol_abs=0.0, tol_rel=0.0, ne
     d.proj = _ptr(proj) if d.N else None
     _lib.call("cn_mesh_visibility", ctypes.byref(d), _stream())
     return count
+
+
+# ---------------------------------------------------------------------------
+# TSDF fusion (additive to ABI v22): cn_tsdf.hip
+def _need_volume(fn, t, name, shape):
+    _need(t, name, ndim=0)
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise RuntimeError(f"{fn}: {name} must be a contiguous fp32 {list(shape)} device tensor (got {t.dtype}, "
+                           f"shape {tuple(t.shape)})")
+
+
+def tsdf_integrate(tsum, wsum, lo, hi, proj, depth, trunc, *, csum=None, color=None, near=MESH_NEAR,
+                   depth_max=math.inf, brick_reject=True):
+    """Fuse the views proj fp32 [N, 3, 4] / depth fp32 [N, h, w] (and color fp32 [N, h, w, 3]) into the running
+    volumes tsum, wsum fp32 [nx, ny, nz] (and csum [nx, ny, nz, 3]) over the box lo .. hi, in place --
+    cn_tsdf_integrate.  A voxel that projects, at depth c >= near, onto a pixel with a finite depth d in
+    (0, depth_max] and d - c >= -trunc adds min(1, (d - c) / trunc) to tsum, 1 to wsum and the pixel's colour to
+    csum.  Bitwise repeatable, and equal to any split of the views over several calls; the volumes are read and
+    written once per call (fusion.VIEWS_PER_CALL: the batch measured fastest).  brick_reject=False turns the
+    wavefront-level frustum skip off (it never changes a result; for measurement)."""
+    _need_volume("tsdf_integrate", tsum, "tsum", tsum.shape)
+    if tsum.dim() != 3:
+        raise RuntimeError(f"tsdf_integrate: tsum must be [nx, ny, nz] (got shape {tuple(tsum.shape)})")
+    dev, dims = tsum.device, tuple(tsum.shape)
+    _need_volume("tsdf_integrate", wsum, "wsum", dims)
+    _need_proj("tsdf_integrate", proj, dev)
+    _need(depth, "depth", ndim=0)
+    if depth.dtype != torch.float32 or depth.dim() != 3 or depth.shape[0] != proj.shape[0] or not depth.is_contiguous():
+        raise RuntimeError(f"tsdf_integrate: depth must be a contiguous fp32 [{proj.shape[0]}, h, w] device tensor (got "
+                           f"{depth.dtype}, shape {tuple(depth.shape)})")
+    if (csum is None) != (color is None):
+        raise RuntimeError("tsdf_integrate: csum and color go together (both or neither)")
+    if csum is not None:
+        _need_volume("tsdf_integrate", csum, "csum", dims + (3,))
+        _need_volume("tsdf_integrate", color, "color", tuple(depth.shape) + (3,))
+    for t, nm in ((wsum, "wsum"), (depth, "depth"), (csum, "csum"), (color, "color")):
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"tsdf_integrate: {nm} on another device")
+    d = _lib.TsdfDesc()
+    d.nx, d.ny, d.nz = dims
+    d.lo, d.hi = _box(lo, hi)
+    d.N, d.h, d.w = depth.shape
+    d.trunc, d.near, d.depth_max, d.no_reject = float(trunc), float(near), float(depth_max), int(not brick_reject)
+    d.tsum, d.wsum, d.csum = _ptr(tsum), _ptr(wsum), _ptr(csum)
+    d.proj, d.depth, d.color = (_ptr(proj), _ptr(depth), _ptr(color)) if d.N else (None, None, _ptr(color))
+    _lib.call("cn_tsdf_integrate", ctypes.byref(d), _stream())
+
+
+def tsdf_finalize(tsum, wsum, csum=None, min_weight=1.0):
+    """u fp32 [nx, ny, nz] = tsum / wsum where wsum >= min_weight (>= 1), NaN elsewhere (unobserved) --
+    cn_tsdf_finalize; with csum also rgb fp32 [nx, ny, nz, 3] = csum / wsum there, 0 elsewhere: (u, rgb)."""
+    _need_volume("tsdf_finalize", tsum, "tsum", tsum.shape)
+    if tsum.dim() != 3:
+        raise RuntimeError(f"tsdf_finalize: tsum must be [nx, ny, nz] (got shape {tuple(tsum.shape)})")
+    dims = tuple(tsum.shape)
+    _need_volume("tsdf_finalize", wsum, "wsum", dims)
+    if csum is not None:
+        _need_volume("tsdf_finalize", csum, "csum", dims + (3,))
+    u = torch.empty_like(tsum)
+    rgb = torch.empty_like(csum) if csum is not None else None
+    d = _lib.TsdfFinalizeDesc()
+    d.nx, d.ny, d.nz = dims
+    d.min_weight = float(min_weight)
+    d.tsum, d.wsum, d.csum, d.u, d.rgb = _ptr(tsum), _ptr(wsum), _ptr(csum), _ptr(u), _ptr(rgb)
+    _lib.call("cn_tsdf_finalize", ctypes.byref(d), _stream())
+    return u if csum is None else (u, rgb)
+
+
+def volume_sample(attr, points, lo, hi, mask=None, fill=0.0):
+    """out fp32 [Q, C]: the trilinear interpolation of attr fp32 [nx, ny, nz, C] (C 1 .. 4; [nx, ny, nz] counts as
+    C = 1) over the box lo .. hi at points fp32 [Q, 3] -- cn_volume_sample; a point outside the box samples the
+    nearest face.  mask: a u volume [nx, ny, nz] whose NaN mean unobserved -- such corners get weight 0, the rest
+    are renormalised, and a point whose observed corners carry no weight gets `fill`."""
+    _need(attr, "attr", ndim=0)
+    if attr.dtype != torch.float32 or attr.dim() not in (3, 4) or not attr.is_contiguous():
+        raise RuntimeError(f"volume_sample: attr must be a contiguous fp32 [nx, ny, nz, C] device tensor (got {attr.dtype}, "
+                           f"shape {tuple(attr.shape)})")
+    dims, C = tuple(attr.shape[:3]), attr.shape[3] if attr.dim() == 4 else 1
+    _need_cloud("volume_sample", points, "points")
+    if mask is not None:
+        _need_volume("volume_sample", mask, "mask", dims)
+    if points.device != attr.device or (mask is not None and mask.device != attr.device):
+        raise RuntimeError("volume_sample: attr, points and mask on different devices")
+    out = torch.empty(points.shape[0], C, device=attr.device)
+    d = _lib.VolumeSampleDesc()
+    d.nx, d.ny, d.nz = dims
+    d.C, d.Q, d.fill = C, points.shape[0], float(fill)
+    d.lo, d.hi = _box(lo, hi)
+    d.attr, d.mask = _ptr(attr), _ptr(mask)
+    d.points, d.out = (_ptr(points), _ptr(out)) if d.Q else (None, None)
+    _lib.call("cn_volume_sample", ctypes.byref(d), _stream())
+    return out
 
 
 MESH_SHADE_GREY = 0.8  # the albedo of a mesh shaded without colours

@@ -4,6 +4,9 @@
 // on any indexed triangle list: connected components by label propagation with pointer jumping
 // (cn_mesh_label_init / cn_mesh_label_rounds), the triangles per component (cn_mesh_component_sizes) and the
 // compaction to the kept components through the mesher's scans (cn_mesh_select / cn_mesh_compact).
+// cn_mesh_count_observed / cn_mesh_emit_observed (additive to ABI v22) are the two mesher kernels compiled with
+// OBS = true: NaN in u means unobserved, an edge carries a vertex only between two observed ends and a cell emits
+// triangles only with its eight corners observed (the volumes of cn_tsdf.hip).
 //
 // Reference: NeuSRenderer.extract_geometry / extract_fields (neus_renderer.py:10-37): the interface and the
 // grid (torch.linspace per axis, u[xi, yi, zi], vertices / (resolution - 1) * (max - min) + min).  The
@@ -68,13 +71,16 @@ struct MeshArgs {
 };
 
 // The thread's grid vertex p = (ix, iy, iz), the values at p + o for the eight offsets o = ox + 2 oy + 4 oz
-// (p's own value where p + o is outside the grid) and which of them are inside the grid.
+// (p's own value where p + o is outside the grid) and which of them are inside the grid.  OBS (the *_observed
+// entry points): a NaN value is an unobserved grid vertex, and `have` keeps only the observed ones.
 struct Stencil {
     int ix, iy, iz, p;
     float v[8];
-    int have;  // bit o: p + o is a grid vertex
+    int have;  // bit o: p + o is a grid vertex (OBS: and observed)
+    int grid;  // OBS only -- bit o: p + o is a grid vertex
 };
 
+template <bool OBS>
 __device__ __forceinline__ bool load_stencil(const MeshArgs& a, Stencil* s) {
     const int N = a.nx * a.ny * a.nz;
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -86,17 +92,23 @@ __device__ __forceinline__ bool load_stencil(const MeshArgs& a, Stencil* s) {
     s->ix = r / a.ny;
     const bool hx = s->ix + 1 < a.nx, hy = s->iy + 1 < a.ny, hz = s->iz + 1 < a.nz;
     s->have = 0;
+    if (OBS) s->grid = 0;
 #pragma unroll
     for (int o = 0; o < 8; ++o) {
         const bool ok = (!(o & 1) || hx) && (!(o & 2) || hy) && (!(o & 4) || hz);
         const int q = p + ((o & 1) ? a.ny * a.nz : 0) + ((o & 2) ? a.nz : 0) + ((o & 4) ? 1 : 0);
         s->v[o] = a.u[ok ? q : p];
-        s->have |= ok ? 1 << o : 0;
+        if (OBS) {
+            s->grid |= ok ? 1 << o : 0;
+            s->have |= ok && s->v[o] == s->v[o] ? 1 << o : 0;
+        } else {
+            s->have |= ok ? 1 << o : 0;
+        }
     }
     return true;
 }
 
-// bit o: the value at p + o is below the threshold (strictly: a tie is outside)
+// bit o: the value at p + o is below the threshold (strictly: a tie is outside, and so is a NaN)
 __device__ __forceinline__ int inside_bits(const Stencil& s, float thr) {
     int in = 0;
 #pragma unroll
@@ -104,9 +116,11 @@ __device__ __forceinline__ int inside_bits(const Stencil& s, float thr) {
     return in;
 }
 
-// the 7-bit mask of p's owned edges (slot d - 1, d = dx + 2 dy + 4 dz) whose ends differ
+// the 7-bit mask of p's owned edges (slot d - 1, d = dx + 2 dy + 4 dz) whose ends differ (OBS: and are both observed)
+template <bool OBS>
 __device__ __forceinline__ int edge_mask(const Stencil& s, int in) {
     const int differ = (in ^ ((in & 1) ? 0xff : 0)) & s.have;
+    if (OBS && !(s.have & 1)) return 0;
     return differ >> 1;
 }
 
@@ -116,14 +130,15 @@ __device__ __forceinline__ int tet_mask(int in, int k) {
     return (in & 1) | ((in >> ((c >> 3) & 7)) & 1) << 1 | ((in >> ((c >> 6) & 7)) & 1) << 2 | ((in >> 7) & 1) << 3;
 }
 
+template <bool OBS>
 __global__ void mesh_count_kernel(MeshArgs a) {
     Stencil s;
-    if (!load_stencil(a, &s)) return;
+    if (!load_stencil<OBS>(a, &s)) return;
     const int in = inside_bits(s, a.thr);
-    a.emask[s.p] = (uint8_t)edge_mask(s, in);
-    if (s.have == 0xff) {
+    a.emask[s.p] = (uint8_t)edge_mask<OBS>(s, in);
+    if ((OBS ? s.grid : s.have) == 0xff) {
         int n = 0;
-        if (in != 0 && in != 0xff) {
+        if (in != 0 && in != 0xff && (!OBS || s.have == 0xff)) {  // OBS: a cell with an unobserved corner has no triangle
 #pragma unroll
             for (int k = 0; k < 6; ++k) n += kTet.entry[k * 16 + tet_mask(in, k)] & 3;
         }
@@ -194,14 +209,15 @@ __global__ void scan_apply_kernel(const uint8_t* __restrict__ c, int n, const in
     }
 }
 
+template <bool OBS>
 __global__ void mesh_emit_kernel(MeshArgs a) {
     // output buffers smaller than the counts: nothing is written (the decision is the same in every thread)
     const int64_t V = a.counts[0], T = a.counts[1];
     if (V > a.max_vertices || T > a.max_triangles) return;
     Stencil s;
-    if (!load_stencil(a, &s)) return;
+    if (!load_stencil<OBS>(a, &s)) return;
     const int in = inside_bits(s, a.thr);
-    const int em = edge_mask(s, in);
+    const int em = edge_mask<OBS>(s, in);
     if (em) {
         // the vertices on p's owned edges, ascending by slot
         int id = a.voff[s.p];
@@ -668,25 +684,47 @@ extern "C" size_t cn_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz) {
     return mesh_plan(nx, ny, nz, nullptr).bytes;
 }
 
-extern "C" int cn_mesh_count(const cn_mesh_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream) {
-    int rc = mesh_check("cn_mesh_count", d, workspace, workspace_bytes, false);
+namespace {
+
+template <bool OBS>
+int mesh_count_launch(const char* who, const cn_mesh_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream) {
+    int rc = mesh_check(who, d, workspace, workspace_bytes, false);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const MeshPlan p = mesh_plan(d->nx, d->ny, d->nz, workspace);
     const MeshArgs a = mesh_args(d, p);
-    mesh_count_kernel<<<(p.N + 255) / 256, 256, 0, st>>>(a);
-    if ((rc = check_launch("cn_mesh_count"))) return rc;
-    if ((rc = scan_launch<true>("cn_mesh_count", p.emask, p.N, p.vt, p.vtot, p.voff, d->counts, st))) return rc;
-    return scan_launch<false>("cn_mesh_count", p.tcount, p.C, p.ct, p.ttot, p.toff, d->counts + 1, st);
+    mesh_count_kernel<OBS><<<(p.N + 255) / 256, 256, 0, st>>>(a);
+    if ((rc = check_launch(who))) return rc;
+    if ((rc = scan_launch<true>(who, p.emask, p.N, p.vt, p.vtot, p.voff, d->counts, st))) return rc;
+    return scan_launch<false>(who, p.tcount, p.C, p.ct, p.ttot, p.toff, d->counts + 1, st);
 }
 
-extern "C" int cn_mesh_emit(const cn_mesh_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream) {
-    int rc = mesh_check("cn_mesh_emit", d, workspace, workspace_bytes, true);
+template <bool OBS>
+int mesh_emit_launch(const char* who, const cn_mesh_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream) {
+    int rc = mesh_check(who, d, workspace, workspace_bytes, true);
     if (rc) return rc;
     const MeshPlan p = mesh_plan(d->nx, d->ny, d->nz, workspace);
     const MeshArgs a = mesh_args(d, p);
-    mesh_emit_kernel<<<(p.N + 255) / 256, 256, 0, (hipStream_t)stream>>>(a);
-    return check_launch("cn_mesh_emit");
+    mesh_emit_kernel<OBS><<<(p.N + 255) / 256, 256, 0, (hipStream_t)stream>>>(a);
+    return check_launch(who);
+}
+
+}  // namespace
+
+extern "C" int cn_mesh_count(const cn_mesh_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream) {
+    return mesh_count_launch<false>("cn_mesh_count", d, workspace, workspace_bytes, stream);
+}
+
+extern "C" int cn_mesh_emit(const cn_mesh_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream) {
+    return mesh_emit_launch<false>("cn_mesh_emit", d, workspace, workspace_bytes, stream);
+}
+
+extern "C" int cn_mesh_count_observed(const cn_mesh_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream) {
+    return mesh_count_launch<true>("cn_mesh_count_observed", d, workspace, workspace_bytes, stream);
+}
+
+extern "C" int cn_mesh_emit_observed(const cn_mesh_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream) {
+    return mesh_emit_launch<true>("cn_mesh_emit_observed", d, workspace, workspace_bytes, stream);
 }
 
 extern "C" int cn_mesh_label_init(const cn_mesh_clean_desc* d, cn_stream_t stream) {

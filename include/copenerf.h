@@ -858,6 +858,17 @@ typedef struct cn_mesh_desc {
 size_t cn_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
 int cn_mesh_count(const cn_mesh_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
 int cn_mesh_emit(const cn_mesh_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+/* cn_mesh_count_observed / cn_mesh_emit_observed (additive to ABI v22): the same mesher over a
+ * volume in which NaN means "unobserved" (cn_tsdf_finalize's u) -- the same descriptor, the same
+ * workspace layout and size, the same vertex and triangle order.  An owned edge carries a vertex
+ * only when both its ends are observed (and differ in the mask bit); a cell emits triangles only
+ * when all eight corners are observed.  No vertex coordinate is ever NaN.  A vertex on an edge
+ * whose every surrounding cell was skipped is still emitted and no triangle refers to it: drop
+ * such vertices with cn_mesh_select / cn_mesh_compact at min_triangles >= 1 (a vertex without a
+ * triangle is a component of none).  With no NaN in u the results are bitwise those of
+ * cn_mesh_count / cn_mesh_emit. */
+int cn_mesh_count_observed(const cn_mesh_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+int cn_mesh_emit_observed(const cn_mesh_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
  * Vertex colours (additive to ABI v22): the colour network at surface points, with the
@@ -1199,6 +1210,90 @@ typedef struct cn_mesh_shade_desc {
     uint8_t* shaded_img;                /* [N][h][w][3], or NULL */
 } cn_mesh_shade_desc;
 int cn_mesh_shade(const cn_mesh_shade_desc* d, cn_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
+ * TSDF fusion (additive to ABI v22): per-view depth maps fused into a truncated signed
+ * distance volume, the other way NeuS-family and ScanNet-style evaluations get a mesh (render
+ * or read a depth per view, fuse, mesh what the cameras saw).  The reference has no fusion
+ * code; the yardstick is a float64 restatement.  Cameras are cn_mesh_raster's 3 x 4
+ * projections, depths are its c.
+ *
+ * cn_tsdf_integrate: the running volumes tsum [nx][ny][nz], wsum [nx][ny][nz] and, with colours,
+ * csum [nx][ny][nz][3] (fp32, read and written; zero them before the first call) take in the N
+ * views proj [N][3][4], depth [N][h][w] and color [N][h][w][3] (or NULL, exactly when csum is).
+ * One thread per voxel, z fastest; no workspace, no allocation, no synchronisation.  Voxel
+ * (ix, iy, iz) sits at X_ax = (float)i / (float)(n - 1) * (hi - lo) + lo, all in fp32: the
+ * mesher's vertex map at integer positions, so mesh and volume agree (not cn_grid_points'
+ * linspace rule).  Per view, in view order, in fp32 and in this order:
+ *   1. a = ((P00 x + P01 y) + P02 z) + P03, b and c alike;
+ *   2. skip unless c >= near;
+ *   3. pixel (floor(a / c + 0.5), floor(b / c + 0.5)), as cn_mesh_visibility; skip outside the image;
+ *   4. d = depth[view][py][px]; skip unless d is finite, d > 0 and d <= depth_max ("0 where
+ *      nothing is seen" and "+inf where nothing is seen" both mean no observation; so does NaN);
+ *   5. s = d - c; skip if s < -trunc;
+ *   6. tsum += fminf(1, s / trunc), wsum += 1, csum += color[view][py][px].
+ * A voxel's result depends on nothing but its own sequence of views: there are no atomics, the
+ * result is bitwise repeatable, and one call with N views is bitwise equal to any split of the
+ * same views, in the same order, over several calls (each volume is read once and written once
+ * per call; the batch that was measured fastest: DESIGN.md 3.12.5).  A wavefront's 64 voxels may skip a view as a whole
+ * when their bounding box lies, with a margin far above the fp32 error, behind `near` or off
+ * one side of the image; the skip never changes a result (no_reject = 1 turns it off, for
+ * measurement).  N = 0 is a no-op without a launch.  Any dim below 2, nx ny nz or h w >= 2^31:
+ * CN_ERR_SHAPE; trunc, near > 0 and finite; depth_max > 0, +inf for none.
+ * ------------------------------------------------------------------------ */
+typedef struct cn_tsdf_desc {
+    int32_t nx, ny, nz;
+    float lo[3], hi[3];
+    int32_t N, h, w;
+    const float* proj;                  /* [N][3][4] */
+    const float* depth;                 /* [N][h][w] */
+    const float* color;                 /* [N][h][w][3], or NULL */
+    float trunc, near, depth_max;
+    int32_t no_reject;                  /* 1: no wavefront skips a view (measurement) */
+    float* tsum;                        /* [nx][ny][nz] */
+    float* wsum;                        /* [nx][ny][nz] */
+    float* csum;                        /* [nx][ny][nz][3], NULL exactly when color is */
+} cn_tsdf_desc;
+int cn_tsdf_integrate(const cn_tsdf_desc* d, cn_stream_t stream);
+
+/* cn_tsdf_finalize: u [nx][ny][nz] = tsum / wsum where wsum >= min_weight (min_weight >= 1), NaN
+ * elsewhere ("unobserved": what cn_mesh_*_observed and cn_volume_sample's mask read); with rgb
+ * (optional, needs csum) rgb [nx][ny][nz][3] = csum / wsum there and 0 elsewhere.  The sign is
+ * the mesher's: positive in front of the surface, so triangle normals point out of it.  One
+ * thread per voxel, no workspace. */
+typedef struct cn_tsdf_finalize_desc {
+    int32_t nx, ny, nz;
+    float min_weight;
+    const float* tsum;
+    const float* wsum;
+    const float* csum;                  /* or NULL */
+    float* u;
+    float* rgb;                         /* or NULL */
+} cn_tsdf_finalize_desc;
+int cn_tsdf_finalize(const cn_tsdf_finalize_desc* d, cn_stream_t stream);
+
+/* cn_volume_sample: out [Q][C] (1 <= C <= 4) = the trilinear interpolation of attr
+ * [nx][ny][nz][C] at points [Q][3], one thread per point, no atomics, no workspace.  Index
+ * position per axis, in fp32: g = (x - lo) / (hi - lo) * (n - 1), clamped to [0, n - 1] (a point
+ * outside the box samples its nearest face); i0 = min((int)floorf(g), n - 2); f = g - i0.  Corner
+ * o = ox + 2 oy + 4 oz has weight (wx wy) wz with w = f where the offset is 1, 1 - f where it is
+ * 0; out = the sum over o = 0 .. 7, in that order, of weight x attr.  With mask [nx][ny][nz] (a u
+ * volume, NaN meaning unobserved) a corner that is unobserved gets weight 0 and is not read,
+ * and the sum is divided by the sum of the remaining weights; a point whose observed corners
+ * carry no weight (none is observed, or only corners of weight 0) gets `fill` in every channel.
+ * hi > lo on every axis; Q < 2^31. */
+typedef struct cn_volume_sample_desc {
+    int32_t nx, ny, nz;
+    int32_t C;
+    float lo[3], hi[3];
+    const float* attr;                  /* [nx][ny][nz][C] */
+    const float* mask;                  /* [nx][ny][nz], or NULL */
+    int64_t Q;
+    const float* points;                /* [Q][3] */
+    float fill;
+    float* out;                         /* [Q][C] */
+} cn_volume_sample_desc;
+int cn_volume_sample(const cn_volume_sample_desc* d, cn_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
  * Pose refinement (ABI v17): compute_loss_and_warp_image
