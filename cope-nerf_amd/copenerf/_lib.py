@@ -210,6 +210,17 @@ class CloudStatsDesc(ctypes.Structure):
     ]
 
 
+class CloudTransformDesc(ctypes.Structure):
+    _fields_ = [("N", c_i64), ("points", c_ptr), ("matrix", c_f32 * 12), ("out", c_ptr)]
+
+
+class IcpAccumulateDesc(ctypes.Structure):
+    _fields_ = [
+        ("Q", c_i64), ("N", c_i64), ("source", c_ptr), ("targets", c_ptr), ("target_normals", c_ptr), ("index", c_ptr),
+        ("matrix", c_f32 * 12), ("mode", c_i32), ("pivot", ctypes.c_double * 3), ("out", c_ptr),
+    ]
+
+
 class MeshRasterDesc(ctypes.Structure):
     _fields_ = [
         ("V", c_i64), ("T", c_i64), ("vertices", c_ptr), ("triangles", c_ptr), ("N", c_i32), ("h", c_i32), ("w", c_i32),
@@ -377,6 +388,9 @@ SIGNATURES = {
     "cn_cloud_stats": (c_i32, [ctypes.POINTER(CloudStatsDesc), c_ptr, c_i64, c_ptr]),
     "cn_cloud_normal_stats_workspace_bytes": (ctypes.c_size_t, [c_i64]),
     "cn_cloud_normal_stats": (c_i32, [ctypes.POINTER(CloudNormalStatsDesc), c_ptr, c_i64, c_ptr]),
+    "cn_cloud_transform": (c_i32, [ctypes.POINTER(CloudTransformDesc), c_ptr]),
+    "cn_icp_accumulate_workspace_bytes": (ctypes.c_size_t, [c_i64]),
+    "cn_icp_accumulate": (c_i32, [ctypes.POINTER(IcpAccumulateDesc), c_ptr, c_i64, c_ptr]),
     "cn_mesh_select_mask": (c_i32, [ctypes.POINTER(MeshCleanDesc), c_ptr, c_ptr, c_i64, c_ptr]),
     "cn_mesh_raster_workspace_bytes": (ctypes.c_size_t, [c_i64, c_i64, c_i32, c_i32, c_i32, c_i32]),
     "cn_mesh_raster": (c_i32, [ctypes.POINTER(MeshRasterDesc), c_ptr, c_i64, c_ptr]),

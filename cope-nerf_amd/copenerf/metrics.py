@@ -12,6 +12,10 @@
   geometry        nearest_distances (exact nearest neighbour between two clouds: cn_nn_grid_build /
                   cn_nn_query) and mesh_geometry_metrics (Chamfer distance in the DTU style, precision /
                   recall / F-score in the Tanks and Temples style) on the device; the reference has none;
+  registration    icp_register / icp_register_stages (ICP of a cloud onto a target cloud: cn_cloud_transform,
+                  the nearest-neighbour query and cn_icp_accumulate on the device, icp_solve_point /
+                  icp_solve_plane in float64 on the host), which mesh_geometry_metrics(icp=...) refines its
+                  transform with, as the Tanks and Temples protocol does;
   evaluate        render the test views (inference.render_image), keep the maps on the device, run the
                   above and merge the dictionaries in eval.py:264-267's order; write_results writes
                   results.txt (eval.py:268-270).
@@ -528,10 +532,271 @@ def geometry_from_stats(pred, gt, area):
             "n_pred_far": int(np_ - npn), "n_gt_far": int(ng - ngn), "area": area}
 
 
+# ---------------------------------------------------------------------------
+# ICP registration: the solvers (host, float64) and the loop (device passes, one 256-byte read-back each)
+ICP_RANK_TOL = 1e-9  # a system whose smallest needed singular / eigen value is below this share of the largest
+
+
+def icp_solve_point(sums, with_scale=False, pivot=None):
+    """The 4 x 4 increment of one point-to-point iteration from cn_icp_accumulate's mode-0 sums (32 numbers; the
+    layout is copenerf.h's), taken about `pivot` (3 numbers, default the origin): Kabsch -- with_scale: Umeyama,
+    the scale from the source variance -- by a 3 x 3 SVD in float64 with the reflection guard.  The increment
+    takes the transformed source p' onto the targets: q ~ s R (p' - pivot - mean_p) + mean_q + pivot.
+    ValueError for fewer than 3 pairs and for a source or target set without a plane's worth of spread
+    (collinear or coincident points)."""
+    s_ = np.asarray(sums, dtype=np.float64).reshape(-1)
+    c = np.zeros(3) if pivot is None else np.asarray(pivot, dtype=np.float64).reshape(3)
+    n = s_[0]
+    if n < 3:
+        raise ValueError(f"icp_solve_point: {int(n)} correspondences, at least 3 needed")
+    mp, mq = s_[2:5] / n, s_[5:8] / n
+    C = s_[8:17].reshape(3, 3) / n - np.outer(mq, mp)
+    var = s_[17] / n - mp @ mp
+    U, D, Vt = np.linalg.svd(C)
+    if not (np.isfinite(D).all() and D[0] > 0.0 and D[1] > ICP_RANK_TOL * D[0] and var > 0.0):
+        raise ValueError(f"icp_solve_point: rank-deficient system (singular values {D.tolist()}): the pairs are "
+                         "collinear or coincident")
+    S = np.eye(3)
+    if np.linalg.det(U) * np.linalg.det(Vt) < 0:
+        S[2, 2] = -1
+    R = U @ S @ Vt
+    scale = float(np.trace(np.diag(D) @ S) / var) if with_scale else 1.0
+    M = np.eye(4)
+    M[:3, :3] = scale * R
+    M[:3, 3] = (mq + c) - scale * (R @ (mp + c))
+    return M
+
+
+def _rodrigues(w):
+    th = float(np.linalg.norm(w))
+    K = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    if th < 1e-8:
+        return np.eye(3) + K + 0.5 * (K @ K)
+    return np.eye(3) + (math.sin(th) / th) * K + ((1.0 - math.cos(th)) / (th * th)) * (K @ K)
+
+
+def icp_solve_plane(sums, pivot=None):
+    """The 4 x 4 increment of one point-to-plane iteration from cn_icp_accumulate's mode-1 sums: the 6 x 6
+    normal equations (sum J^T J) x = -(sum J^T r), x = (rotation vector w, translation v), by Cholesky; w is
+    turned into an exact rotation (Rodrigues) about `pivot` (default the origin), then v is added:
+    p'' = R (p' - pivot) + pivot + v.  ValueError for fewer than 6 pairs and for a rank-deficient system (e.g.
+    every normal the same: a single plane fixes 3 of the 6 freedoms)."""
+    s_ = np.asarray(sums, dtype=np.float64).reshape(-1)
+    c = np.zeros(3) if pivot is None else np.asarray(pivot, dtype=np.float64).reshape(3)
+    n = s_[0]
+    if n < 6:
+        raise ValueError(f"icp_solve_plane: {int(n)} correspondences, at least 6 needed")
+    A = np.zeros((6, 6))
+    A[np.triu_indices(6)] = s_[3:24]
+    A = A + np.triu(A, 1).T
+    b = s_[24:30]
+    ev = np.linalg.eigvalsh(A)
+    if not (np.isfinite(ev).all() and ev[-1] > 0.0 and ev[0] > ICP_RANK_TOL * ev[-1]):
+        raise ValueError(f"icp_solve_plane: rank-deficient system (eigenvalues {ev.tolist()}): the normals do not "
+                         "constrain all six freedoms")
+    try:
+        L = np.linalg.cholesky(A)
+    except np.linalg.LinAlgError as e:
+        raise ValueError(f"icp_solve_plane: rank-deficient system ({e})") from None
+    x = -np.linalg.solve(L.T, np.linalg.solve(L, b))
+    R = _rodrigues(x[:3])
+    M = np.eye(4)
+    M[:3, :3] = R
+    M[:3, 3] = c - R @ c + x[3:]
+    return M
+
+
+class IcpResult:
+    """What icp_register returns: transform (float64 4 x 4 numpy, source frame to target frame), fitness (pairs /
+    points used) and inlier_rmse of that transform, iterations (solves applied), converged, and history, the
+    (fitness, rmse) every iteration started from."""
+
+    def __init__(self, transform, fitness, inlier_rmse, iterations, converged, history):
+        self.transform, self.fitness, self.inlier_rmse = transform, fitness, inlier_rmse
+        self.iterations, self.converged, self.history = iterations, converged, history
+
+    def __repr__(self):
+        return (f"IcpResult(fitness={self.fitness}, inlier_rmse={self.inlier_rmse}, iterations={self.iterations}, "
+                f"converged={self.converged})")
+
+
+def _mat4(fn, T):
+    M = np.array(T.detach().cpu() if torch.is_tensor(T) else T, dtype=np.float64)
+    if M.shape != (4, 4) or not np.isfinite(M).all():
+        raise ValueError(f"{fn}: a finite 4 x 4 transform expected, got shape {M.shape}")
+    return M
+
+
+ICP_MODES = {"point": 0, "plane": 1}
+
+
+def icp_register(source, target, *, max_corr_dist, init=None, mode="point", with_scale=False, target_normals=None,
+                 max_iters=50, tol=1e-6, stride=1, cell=None):
+    """ICP registration of source fp32 [Q, 3] onto target fp32 [N, 3] (device tensors): the similarity T (rigid
+    unless with_scale) that minimises, over the pairs (T p, its nearest target within max_corr_dist), the
+    point-to-point distances (mode "point") or the distances to the targets' tangent planes (mode "plane", with
+    target_normals fp32 [N, 3], any length).  The target grid is built once (nn_cell_size, as nearest_distances;
+    `cell` overrides its edge), the loop starts from `init` (a 4 x 4, default the identity) over source[::stride],
+    and an iteration is cloud_transform -> binning the moved cloud on the target's grid -> nn_query on the binned
+    records -> icp_accumulate -> one 256-byte read-back -> icp_solve_point / icp_solve_plane about the centre of the
+    target's bounding box (a correspondence kernel fused with the transform was measured slower than these three
+    calls: DESIGN.md 3.12.6).  T is kept in float64 here and
+    composed as T <- dT T; the device gets the fp32 rounding of the current T each time, so rounding does not
+    accumulate.  fitness = pairs / points used and inlier_rmse = sqrt(sum |T p - q|^2 / pairs) are those of the
+    transform an iteration starts from; the loop stops when both change by less than tol between two consecutive
+    iterations (converged, and the transform returned is the one they were measured at), or after max_iters
+    solves (then one more pass measures the transform returned).  Returns an IcpResult."""
+    fn = "icp_register"
+    if mode not in ICP_MODES:
+        raise ValueError(f"{fn}: mode {mode!r} (point or plane)")
+    if with_scale and mode == "plane":
+        raise ValueError(f"{fn}: with_scale needs mode 'point' (the point-to-plane step is rigid)")
+    if not max_corr_dist > 0:
+        raise ValueError(f"{fn}: max_corr_dist {max_corr_dist}")
+    stride, max_iters = int(stride), int(max_iters)
+    if stride < 1 or max_iters < 1:
+        raise ValueError(f"{fn}: stride {stride}, max_iters {max_iters}")
+    ops._need_cloud(fn, source, "source")
+    ops._need_cloud(fn, target, "target")
+    if mode == "plane":
+        if target_normals is None:
+            raise ValueError(f"{fn}: mode 'plane' needs target_normals")
+        ops._need_cloud(fn, target_normals, "target_normals")
+        if target_normals.shape[0] != target.shape[0]:
+            raise ValueError(f"{fn}: {target_normals.shape[0]} normals for {target.shape[0]} targets")
+    if source.device != target.device:
+        raise RuntimeError(f"{fn}: source and target on different devices")
+    T = np.eye(4) if init is None else _mat4(fn, init)
+    src = source if stride == 1 else source[::stride].contiguous()
+    Q, N = src.shape[0], target.shape[0]
+    if Q == 0 or N == 0:
+        raise ValueError(f"{fn}: {Q} source points and {N} targets")
+    box = torch.stack([target.amin(0), target.amax(0)]).tolist()
+    if not all(math.isfinite(x) for x in box[0] + box[1]):
+        raise ValueError(f"{fn}: the targets must be finite")
+    if cell is None:
+        cell, dims = nn_cell_size(box[0], box[1], N)
+    else:
+        cell = float(cell)
+        if not cell > 0.0:
+            raise ValueError(f"{fn}: cell {cell}")
+        dims = tuple(int((h - l) / cell) + 1 for l, h in zip(*box))
+        if dims[0] * dims[1] * dims[2] > ops.NN_MAX_CELLS:
+            raise ValueError(f"{fn}: cell {cell} gives {dims} cells, more than 2^26")
+    grid = ops.nn_grid(target, box[0], cell, dims)
+    pivot = [0.5 * (l + h) for l, h in zip(*box)]
+    m = ICP_MODES[mode]
+    normals = target_normals if m == 1 else None
+
+    def measure(T):
+        binned = ops.nn_grid(ops.cloud_transform(src, T), box[0], cell, dims)
+        _, index = ops.nn_query(grid, binned.sorted, max_corr_dist, records=True)
+        sums = ops.icp_accumulate(src, target, index, T, pivot, m, normals).tolist()
+        n = sums[0]
+        return sums, n / Q, math.sqrt(sums[1] / n) if n > 0 else float("nan")
+
+    history, converged, iterations = [], False, 0
+    while True:
+        sums, fitness, rmse = measure(T)
+        history.append((fitness, rmse))
+        if len(history) > 1 and abs(fitness - history[-2][0]) < tol and abs(rmse - history[-2][1]) < tol:
+            converged = True
+        if converged or iterations == max_iters:
+            break
+        try:
+            dT = icp_solve_point(sums, with_scale, pivot) if m == 0 else icp_solve_plane(sums, pivot)
+        except ValueError as e:
+            raise ValueError(f"{fn}: iteration {iterations} ({Q} points, max_corr_dist {max_corr_dist}, fitness "
+                             f"{fitness}): {e}") from None
+        T = dT @ T
+        iterations += 1
+    return IcpResult(T, fitness, rmse, iterations, converged, history)
+
+
+def icp_register_stages(source, target, stages, **common):
+    """icp_register once per dict of `stages`, coarse to fine: a stage may override max_corr_dist, stride,
+    max_iters and mode, takes everything else from `common`, and starts from the previous stage's transform (the
+    first from common's init).  Returns the last stage's IcpResult, its history the stages' histories joined and
+    its iterations their sum."""
+    stages = list(stages)
+    if not stages:
+        raise ValueError("icp_register_stages: no stages")
+    kw = dict(common)
+    history, iterations, res = [], 0, None
+    for st in stages:
+        extra = set(st) - {"max_corr_dist", "stride", "max_iters", "mode"}
+        if extra:
+            raise ValueError(f"icp_register_stages: a stage may set max_corr_dist, stride, max_iters and mode, not {sorted(extra)}")
+        res = icp_register(source, target, **{**kw, **st})
+        kw["init"] = res.transform
+        history += res.history
+        iterations += res.iterations
+    res.history, res.iterations = history, iterations
+    return res
+
+
+ICP_KEYS = ("icp_fitness", "icp_rmse", "icp_iterations", "icp_converged", "transform")
+
+
+def _apply_transform(vertices, transform, dev):
+    M = torch.as_tensor(np.asarray(transform.detach().cpu() if torch.is_tensor(transform) else transform,
+                                   dtype=np.float64), dtype=torch.float32).to(dev)
+    if M.shape != (4, 4):
+        raise ValueError(f"mesh_geometry_metrics: transform must be 4 x 4, got {tuple(M.shape)}")
+    return (vertices @ M[:3, :3].T + M[:3, 3]).contiguous()
+
+
+def _icp_refine(icp, vertices, triangles, gt_points, gt_normals, transform, n_samples, density, seed, dev):
+    """mesh_geometry_metrics' registration step: (the composed 4 x 4, the IcpResult).  The registration samples are
+    the evaluation sampler's for Philox (seed, offset 4 S), S the evaluation's sample count under the initial
+    transform -- the evaluation draws at offset 0, so the two never share a counter."""
+    icp = dict(icp)
+    stages = icp.pop("stages", None)
+    if (stages is None) == ("max_corr_dist" not in icp):
+        raise ValueError("mesh_geometry_metrics: icp takes stages or a single max_corr_dist")
+    if stages is None:
+        stages = [{"max_corr_dist": icp.pop("max_corr_dist")}]
+    n_reg = int(icp.pop("n_samples", 0))
+    if n_reg < 1 or n_reg >= 2 ** 31:
+        raise ValueError(f"mesh_geometry_metrics: icp n_samples {n_reg}")
+    plane = icp.get("mode") == "plane" or any(st.get("mode") == "plane" for st in stages)
+    if plane:
+        if gt_normals is None:
+            raise ValueError("mesh_geometry_metrics: icp mode 'plane' needs gt_normals")
+        icp["target_normals"] = gt_normals
+    # The mesh is transformed and its area scanned here under the INITIAL transform, for the registration samples, and
+    # once more by the caller under the refined one, for the evaluation: two passes over the vertices and triangles,
+    # small beside the registration.  With `density` the S that fixes the registration's Philox offset is therefore
+    # the initial transform's, while the evaluation's own S comes from the refined area (they differ only when the
+    # registration changes the scale).
+    base = np.eye(4) if transform is None else _mat4("mesh_geometry_metrics", transform)
+    moved = vertices if transform is None else _apply_transform(vertices, transform, dev)
+    if triangles.shape[0] == 0:
+        raise ValueError("mesh_geometry_metrics: a mesh without triangles")
+    handle, area_dev = ops.mesh_area(moved, triangles)
+    if n_samples is not None:
+        S = int(n_samples)
+    else:
+        S = int(math.ceil(float(density) * float(area_dev.item())))
+    if S < 1 or S >= 2 ** 31:
+        raise ValueError(f"mesh_geometry_metrics: {S} samples")
+    philox = torch.tensor([int(seed), 4 * S], dtype=torch.uint64, device=dev)
+    reg, _ = ops.mesh_sample(handle, n_reg, philox)
+    res = icp_register_stages(reg, gt_points, stages, **icp)
+    return res.transform @ base, res
+
+
+def _with_icp(res, icp_res, transform):
+    if icp_res is not None:
+        res.update(zip(ICP_KEYS, (icp_res.fitness, icp_res.inlier_rmse, icp_res.iterations, icp_res.converged,
+                                  np.asarray(transform, dtype=np.float64).tolist())))
+    return res
+
+
 def mesh_geometry_metrics(vertices, triangles, gt_points, *, threshold, max_dist=math.inf, n_samples=None,
                           density=None, seed=0, transform=None, crop_min=None, crop_max=None, cull_views=None,
                           cull_resolution=None, cull_gt=False, cull_min_views=1, cull_tol_abs=None, cull_tol_rel=None,
-                          gt_normals=None):
+                          gt_normals=None, icp=None):
     """Geometry metrics of a triangle mesh against a ground-truth cloud, all on the device.  vertices fp32
     [V, 3], triangles int32 [T, 3] (NeuSRenderer.extract_geometry's output as it is) and gt_points fp32 [N, 3]
     are device tensors.  The mesh is sampled uniformly by area (cn_mesh_area / cn_mesh_sample, Philox seed
@@ -557,7 +822,16 @@ def mesh_geometry_metrics(vertices, triangles, gt_points, *, threshold, max_dist
       normal_accuracy      mean |n_sample . n_gt[nearest]| from the mesh samples to the ground truth;
       normal_completeness  the same from the ground truth to the mesh samples;  normal_consistency: their mean;
       n_pred_normal, n_gt_normal  the pairs counted (pairs with a zero or non-finite normal are left out).
-    Without gt_normals the dict has exactly the keys above."""
+    Without gt_normals the dict has exactly the keys above.
+    icp: a dict with `stages` (a list of icp_register_stages' dicts, coarse to fine) or a single max_corr_dist,
+    n_samples (the registration samples) and icp_register's keywords (mode, with_scale, max_iters, tol, stride,
+    cell).  After culling and `transform`, n_samples registration samples are drawn from the mesh by the same
+    sampler (seed `seed`, Philox offset 4 S with S the evaluation's sample count under `transform`; the evaluation
+    draws at offset 0), registered to gt_points (mode "plane" uses gt_normals), the result is composed onto
+    `transform`, and everything above goes on with the refined transform.  cull_gt keeps using the initial
+    transform: the ground truth is filtered before the registration that refines it.  The dict then gains
+    icp_fitness, icp_rmse, icp_iterations, icp_converged and transform (the composed 4 x 4 as nested lists).
+    With icp=None nothing changes."""
     if gt_normals is not None:
         ops._need_cloud("mesh_geometry_metrics", gt_normals, "gt_normals")
         if gt_normals.shape[0] != gt_points.shape[0]:
@@ -587,12 +861,12 @@ def mesh_geometry_metrics(vertices, triangles, gt_points, *, threshold, max_dist
             if gt_normals is not None:
                 gt_normals = gt_normals[seen > 0].contiguous()
             gt_points = gt_points[seen > 0].contiguous()
+    icp_res = None
+    if icp is not None:
+        transform, icp_res = _icp_refine(icp, vertices, triangles, gt_points, gt_normals, transform, n_samples, density,
+                                         seed, dev)
     if transform is not None:
-        M = torch.as_tensor(np.asarray(transform.detach().cpu() if torch.is_tensor(transform) else transform,
-                                       dtype=np.float64), dtype=torch.float32).to(dev)
-        if M.shape != (4, 4):
-            raise ValueError(f"mesh_geometry_metrics: transform must be 4 x 4, got {tuple(M.shape)}")
-        vertices = (vertices @ M[:3, :3].T + M[:3, 3]).contiguous()
+        vertices = _apply_transform(vertices, transform, dev)
     if triangles.shape[0] == 0:
         raise ValueError("mesh_geometry_metrics: a mesh without triangles")
     handle, area_dev = ops.mesh_area(vertices, triangles)
@@ -615,13 +889,13 @@ def mesh_geometry_metrics(vertices, triangles, gt_points, *, threshold, max_dist
         pred = _cloud_side(samples, gt_points, threshold, max_dist, crop_min, crop_max)
         gt = _cloud_side(gt_points, samples, threshold, max_dist, crop_min, crop_max)
         both = torch.stack([pred, gt]).tolist()
-        return geometry_from_stats(both[0], both[1], area)
+        return _with_icp(geometry_from_stats(both[0], both[1], area), icp_res, transform)
     pred, pred_n = _cloud_side_normals(samples, gt_points, threshold, max_dist, crop_min, crop_max, sample_normals, gt_normals)
     gt, gt_n = _cloud_side_normals(gt_points, samples, threshold, max_dist, crop_min, crop_max, gt_normals, sample_normals)
     both = torch.stack([pred, gt]).tolist()
     res = geometry_from_stats(both[0], both[1], area)
     res.update(normal_geometry_from_stats(*torch.stack([pred_n, gt_n]).tolist()))
-    return res
+    return _with_icp(res, icp_res, transform)
 
 
 # ---------------------------------------------------------------------------

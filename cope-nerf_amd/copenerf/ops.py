@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1509,6 +1510,76 @@ def cloud_normal_stats(query_normals, target_normals, index, dist, max_dist=math
     lib = _lib.load()
     ws = _workspace(lib.cn_cloud_normal_stats_workspace_bytes(d.Q), dev)
     _lib.check(lib.cn_cloud_normal_stats(ctypes.byref(d), _ptr(ws), ws.numel(), _stream()), "cn_cloud_normal_stats")
+    return out
+
+
+# ---------------------------------------------------------------------------
+# ICP registration (additive to ABI v22): cn_mesh_eval.hip
+ICP_SUMS = 32
+
+
+def _sim12(fn, T):
+    """The 12 fp32 numbers of a 4 x 4 similarity (numpy or tensor, any float dtype): its top three rows, rounded
+    to fp32 once, here."""
+    M = np.asarray(T.detach().cpu() if torch.is_tensor(T) else T, dtype=np.float64)
+    if M.shape != (4, 4):
+        raise RuntimeError(f"{fn}: the transform must be 4 x 4, got {M.shape}")
+    return (_lib.c_f32 * 12)(*M[:3].astype(np.float32).reshape(-1).tolist())
+
+
+def cloud_transform(points, T, out=None):
+    """cn_cloud_transform: fp32 [N, 3] = the 4 x 4 similarity T applied to points fp32 [N, 3], by the one device
+    function icp_accumulate applies it with (an ICP iteration's correspondences are nn_query over this output)."""
+    _need_cloud("cloud_transform", points, "points")
+    if out is None:
+        out = torch.empty_like(points)
+    else:
+        _need_cloud("cloud_transform", out, "out")
+        if out.shape != points.shape or out.device != points.device:
+            raise RuntimeError("cloud_transform: out must match points")
+    d = _lib.CloudTransformDesc()
+    d.N, d.matrix = points.shape[0], _sim12("cloud_transform", T)
+    d.points, d.out = (_ptr(points), _ptr(out)) if d.N else (None, None)
+    _lib.call("cn_cloud_transform", ctypes.byref(d), _stream())
+    return out
+
+
+def icp_accumulate(source, targets, index, T, pivot, mode, target_normals=None):
+    """cn_icp_accumulate: a device double [32], the sums of one ICP iteration over the pairs (source[i],
+    targets[index[i]]) with index[i] >= 0 (nn_query's index over cloud_transform(source, T)), the source taken through
+    the 4 x 4 similarity T, relative to pivot
+    (3 numbers).  mode 0: point-to-point, mode 1: point-to-plane with target_normals fp32 [N, 3]; the slots are
+    laid out in copenerf.h."""
+    _need_cloud("icp_accumulate", source, "source")
+    _need_cloud("icp_accumulate", targets, "targets")
+    _need(index, "index", ndim=0)
+    dev = source.device
+    d = _lib.IcpAccumulateDesc()
+    d.Q, d.N = source.shape[0], targets.shape[0]
+    if index.dtype != torch.int32 or tuple(index.shape) != (d.Q,) or not index.is_contiguous():
+        raise RuntimeError(f"icp_accumulate: index must be a contiguous int32 [{d.Q}] device tensor (got {index.dtype} "
+                           f"{tuple(index.shape)})")
+    if mode not in (0, 1):
+        raise RuntimeError(f"icp_accumulate: mode {mode} (0 point-to-point, 1 point-to-plane)")
+    if mode == 1:
+        if target_normals is None:
+            raise RuntimeError("icp_accumulate: mode 1 needs target_normals")
+        _need_cloud("icp_accumulate", target_normals, "target_normals")
+        if target_normals.shape[0] != d.N:
+            raise RuntimeError(f"icp_accumulate: {target_normals.shape[0]} normals for {d.N} targets")
+        d.target_normals = _ptr(target_normals) if d.N else None
+    if any(t.device != dev for t in (targets, index) + ((target_normals,) if mode == 1 else ())):
+        raise RuntimeError("icp_accumulate: tensors on different devices")
+    if d.Q:
+        d.source, d.index = _ptr(source), _ptr(index)
+    d.targets = _ptr(targets) if d.N else None
+    d.matrix, d.mode = _sim12("icp_accumulate", T), int(mode)
+    d.pivot = (ctypes.c_double * 3)(*[float(x) for x in pivot])
+    out = torch.empty(ICP_SUMS, dtype=torch.float64, device=dev)
+    d.out = _ptr(out)
+    lib = _lib.load()
+    ws = _workspace(lib.cn_icp_accumulate_workspace_bytes(d.Q), dev)
+    _lib.check(lib.cn_icp_accumulate(ctypes.byref(d), _ptr(ws), ws.numel(), _stream()), "cn_icp_accumulate")
     return out
 
 

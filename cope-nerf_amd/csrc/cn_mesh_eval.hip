@@ -2,6 +2,9 @@
 // triangle list (cn_mesh_area / cn_mesh_sample), the exact nearest neighbour between two point clouds through a
 // uniform grid (cn_nn_grid_build / cn_nn_query) and the statistics Chamfer distance and F-score are made of
 // (cn_cloud_stats).  The reference has no geometry metric; the yardstick is float64 brute force (tests/mesh_eval_ref.py).
+// ICP registration of a cloud to the targets of such a grid sits on the same search: a similarity applied by one
+// device function (cn_cloud_transform; the correspondences are cn_nn_query over its output) and the reduction of the
+// pairs into the 32 sums of a closed-form step (cn_icp_accumulate); the yardstick is tests/icp_ref.py.
 //
 // Determinism.  The area scan is a nest of SEQUENTIAL sums, not a tree: a thread sums its 4 triangles in order,
 // a wave its 64 threads in lane order, a tile its 4 waves in order, and one wave the tile totals in order; every
@@ -623,6 +626,156 @@ __global__ void __launch_bounds__(kStatsThreads) normal_stats_final_kernel(int n
     }
 }
 
+// ---- ICP registration: the transform -------------------------------------------------------------------
+
+struct Sim {
+    float m[12];  // row-major 3 x 4: s R in the left 3 x 3, t in the last column
+};
+
+// The ONLY place a similarity is applied to a point: row r of m is (a, b, c, t) and
+//   o_r = fmaf(c, z, fmaf(b, y, fmaf(a, x, t)))
+// -- t first, then x, y, z, each step one rounding.  cloud_transform_kernel and icp_partial_kernel both call it, so
+// the same point under the same matrix is the same three floats in each: the sums are over the points the search saw.
+__device__ __forceinline__ void sim_apply(const Sim& s, float x, float y, float z, float* o) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+        o[r] = fmaf(s.m[r * 4 + 2], z, fmaf(s.m[r * 4 + 1], y, fmaf(s.m[r * 4], x, s.m[r * 4 + 3])));
+}
+
+// one thread per point; a thread reads its point before it writes it, so out may be points
+__global__ void __launch_bounds__(256) cloud_transform_kernel(int64_t N, const float* pts, Sim s, float* out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    float o[3];
+    sim_apply(s, pts[i * 3], pts[i * 3 + 1], pts[i * 3 + 2], o);
+    out[i * 3] = o[0];
+    out[i * 3 + 1] = o[1];
+    out[i * 3 + 2] = o[2];
+}
+
+// ---- ICP registration: the sums of a closed-form solve ---------------------------------------------------
+
+constexpr int kIcpSums = 32;
+
+struct IcpArgs {
+    int64_t Q, N;
+    const float* src;
+    const float* tgt;
+    const float* nrm;
+    const int32_t* index;
+    Sim sim;
+    double c[3];
+    double* part;  // [blocks][32]
+    double* out;   // [32]
+};
+
+// launch 1, laid out as stats_partial_kernel over the source in its ORIGINAL order.  Every term is formed in
+// double from the fp32 p' = sim_apply(source[i]), q = targets[index[i]] and (MODE 1) the fp32 unit normal,
+// relative to the pivot c.  An index outside [0, N) -- -1, or anything a foreign array holds -- gathers nothing.
+// The slots (copenerf.h):  MODE 0: 0 n, 1 sum |p' - q|^2, 2..4 sum (p' - c), 5..7 sum (q - c),
+// 8..16 sum (q - c)(p' - c)^T row-major, 17 sum |p' - c|^2.  MODE 1: 0 n, 1 sum |p' - q|^2, 2 sum r^2,
+// 3..23 the upper triangle of sum J^T J row by row, 24..29 sum J^T r, 30 the pairs left out for their normal.
+// The two counts are per-thread integers (a thread sees fewer than 2^31 / 256 points): 29 doubles at most per
+// thread, no atomics, no LDS but block_sum_fixed's.
+template <int MODE>
+__global__ void __launch_bounds__(kStatsThreads) icp_partial_kernel(IcpArgs a) {
+    __shared__ double sh[kStatsThreads / kWave];
+    constexpr int kAcc = MODE == 0 ? 17 : 29;  // the double sums: slot k + 1 is v[k] (slots 1 .. 17, or 1 .. 29)
+    const int64_t stride = (int64_t)gridDim.x * kStatsThreads;
+    double v[kAcc];
+#pragma unroll
+    for (int k = 0; k < kAcc; ++k) v[k] = 0.0;
+    int n = 0, left = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kStatsThreads + threadIdx.x; i < a.Q; i += stride) {  // bound: ceil(Q / stride)
+        const int32_t j = a.index[i];
+        if (j < 0 || j >= a.N) continue;  // (no pair, or an index past the targets: nothing is read)
+        float pf[3];
+        sim_apply(a.sim, a.src[i * 3], a.src[i * 3 + 1], a.src[i * 3 + 2], pf);
+        double p[3], q[3], e[3];
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) {
+            const float qf = a.tgt[(int64_t)j * 3 + ax];
+            e[ax] = (double)pf[ax] - (double)qf;
+            p[ax] = (double)pf[ax] - a.c[ax];
+            q[ax] = (double)qf - a.c[ax];
+        }
+        const double e2 = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+        if (MODE == 0) {
+            n += 1;
+            v[0] = v[0] + e2;
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                v[1 + ax] = v[1 + ax] + p[ax];
+                v[4 + ax] = v[4 + ax] + q[ax];
+#pragma unroll
+                for (int bx = 0; bx < 3; ++bx) v[7 + ax * 3 + bx] = v[7 + ax * 3 + bx] + q[ax] * p[bx];
+            }
+            v[16] = v[16] + ((p[0] * p[0] + p[1] * p[1]) + p[2] * p[2]);
+        } else {
+            float nf[3];
+            if (!unit3(a.nrm + (int64_t)j * 3, nf)) {
+                left += 1;
+                continue;
+            }
+            const double nx = nf[0], ny = nf[1], nz = nf[2];
+            double J[6];
+            J[0] = p[1] * nz - p[2] * ny;
+            J[1] = p[2] * nx - p[0] * nz;
+            J[2] = p[0] * ny - p[1] * nx;
+            J[3] = nx;
+            J[4] = ny;
+            J[5] = nz;
+            const double r = (e[0] * nx + e[1] * ny) + e[2] * nz;
+            n += 1;
+            v[0] = v[0] + e2;
+            v[1] = v[1] + r * r;
+            int k = 2;
+#pragma unroll
+            for (int x = 0; x < 6; ++x)
+#pragma unroll
+                for (int y = x; y < 6; ++y) {
+                    v[k] = v[k] + J[x] * J[y];
+                    ++k;
+                }
+#pragma unroll
+            for (int x = 0; x < 6; ++x) v[23 + x] = v[23 + x] + J[x] * r;  // (k ended at 23)
+        }
+    }
+    double* part = a.part + (int64_t)blockIdx.x * kIcpSums;
+    double s = block_sum_fixed((double)n, sh);
+    if (threadIdx.x == 0) part[0] = s;
+#pragma unroll
+    for (int k = 0; k < kAcc; ++k) {
+        s = block_sum_fixed(v[k], sh);
+        if (threadIdx.x == 0) part[1 + k] = s;
+    }
+    s = block_sum_fixed((double)left, sh);
+    if (threadIdx.x == 0) {
+        for (int k = 1 + kAcc; k < kIcpSums; ++k) part[k] = 0.0;  // bound: at most 14 unused slots
+        if (MODE == 1) part[30] = s;
+    }
+}
+
+// launch 2 (one block): per slot, thread t adds the partials of blocks t, t + 256, ..., then the fixed tree
+__global__ void __launch_bounds__(kStatsThreads) icp_final_kernel(int nb, const double* __restrict__ part,
+                                                                  double* __restrict__ out) {
+    __shared__ double sh[kStatsThreads / kWave];
+    for (int k = 0; k < kIcpSums; ++k) {  // bound: the 32 slots
+        double v = 0.0;
+        for (int b = threadIdx.x; b < nb; b += kStatsThreads) v = v + part[(int64_t)b * kIcpSums + k];  // bound: <= 4
+        const double s = block_sum_fixed(v, sh);
+        if (threadIdx.x == 0) out[k] = s;
+    }
+}
+
+int sim_check(const char* who, const float* m, Sim* s) {
+    for (int i = 0; i < 12; ++i) {
+        CN_REQUIRE(std::isfinite(m[i]), CN_ERR_SHAPE, "%s: matrix[%d] is not finite", who, i);
+        s->m[i] = m[i];
+    }
+    return CN_OK;
+}
+
 }  // namespace
 }  // namespace cn
 
@@ -816,4 +969,65 @@ extern "C" int cn_cloud_normal_stats(const cn_cloud_normal_stats_desc* d, void* 
     if (rc) return rc;
     normal_stats_final_kernel<<<1, kStatsThreads, 0, st>>>(nb, a.part, a.out);
     return check_launch("cn_cloud_normal_stats");
+}
+
+extern "C" int cn_cloud_transform(const cn_cloud_transform_desc* d, cn_stream_t stream) {
+    CN_REQUIRE(d, CN_ERR_ARG, "cn_cloud_transform: null descriptor");
+    CN_REQUIRE(d->N >= 0 && d->N <= kMaxCount, CN_ERR_SHAPE, "cn_cloud_transform: N %lld (in [0, 2^31))", (long long)d->N);
+    Sim s{};
+    int rc = sim_check("cn_cloud_transform", d->matrix, &s);
+    if (rc || d->N == 0) return rc;
+    CN_REQUIRE(d->points && d->out, CN_ERR_ARG, "cn_cloud_transform: null points / out");
+    CN_REQUIRE(((uintptr_t)d->points & 3) == 0 && ((uintptr_t)d->out & 3) == 0, CN_ERR_ALIGN,
+               "cn_cloud_transform: points / out 4-byte aligned");
+    cloud_transform_kernel<<<(unsigned)((d->N + 255) / 256), 256, 0, (hipStream_t)stream>>>(d->N, d->points, s, d->out);
+    return check_launch("cn_cloud_transform");
+}
+
+extern "C" size_t cn_icp_accumulate_workspace_bytes(int64_t Q) {
+    if (Q < 0 || Q > kMaxCount) return 0;
+    return rup_sz((size_t)stats_blocks(Q) * kIcpSums * sizeof(double));
+}
+
+extern "C" int cn_icp_accumulate(const cn_icp_accumulate_desc* d, void* workspace, int64_t workspace_bytes,
+                                 cn_stream_t stream) {
+    CN_REQUIRE(d, CN_ERR_ARG, "cn_icp_accumulate: null descriptor");
+    CN_REQUIRE(d->Q >= 0 && d->Q <= kMaxCount && d->N >= 0 && d->N <= kMaxCount, CN_ERR_SHAPE,
+               "cn_icp_accumulate: Q %lld, N %lld (each in [0, 2^31))", (long long)d->Q, (long long)d->N);
+    CN_REQUIRE(d->mode == 0 || d->mode == 1, CN_ERR_ARG, "cn_icp_accumulate: mode %d (0 point-to-point, 1 point-to-plane)",
+               d->mode);
+    IcpArgs a{};
+    int rc = sim_check("cn_icp_accumulate", d->matrix, &a.sim);
+    if (rc) return rc;
+    for (int i = 0; i < 3; ++i) {
+        CN_REQUIRE(std::isfinite(d->pivot[i]), CN_ERR_SHAPE, "cn_icp_accumulate: pivot[%d] is not finite", i);
+        a.c[i] = d->pivot[i];
+    }
+    CN_REQUIRE(d->out, CN_ERR_ARG, "cn_icp_accumulate: null out");
+    CN_REQUIRE(d->Q == 0 || (d->source && d->index), CN_ERR_ARG, "cn_icp_accumulate: null source / index");
+    CN_REQUIRE(d->Q == 0 || d->N == 0 || d->targets, CN_ERR_ARG, "cn_icp_accumulate: null targets");
+    CN_REQUIRE(d->mode == 0 || d->Q == 0 || d->N == 0 || d->target_normals, CN_ERR_ARG,
+               "cn_icp_accumulate: mode 1 without target_normals");
+    CN_REQUIRE((((uintptr_t)d->source | (uintptr_t)d->targets | (uintptr_t)d->target_normals | (uintptr_t)d->index) & 3) == 0 &&
+                   ((uintptr_t)d->out & 7) == 0,
+               CN_ERR_ALIGN, "cn_icp_accumulate: source / targets / target_normals / index 4-byte, out 8-byte aligned");
+    const size_t need = cn_icp_accumulate_workspace_bytes(d->Q);
+    CN_REQUIRE(workspace && workspace_bytes >= 0 && (size_t)workspace_bytes >= need, CN_ERR_SHAPE,
+               "cn_icp_accumulate: workspace %lld bytes, %zu needed", (long long)workspace_bytes, need);
+    CN_REQUIRE(((uintptr_t)workspace & (kAlign - 1)) == 0, CN_ERR_ALIGN, "cn_icp_accumulate: workspace not 256-byte aligned");
+    a.Q = d->Q;
+    a.N = d->N;
+    a.src = d->source;
+    a.tgt = d->targets;
+    a.nrm = d->target_normals;
+    a.index = d->index;
+    a.part = static_cast<double*>(workspace);
+    a.out = d->out;
+    hipStream_t st = (hipStream_t)stream;
+    const int nb = stats_blocks(d->Q);
+    if (d->mode == 0) icp_partial_kernel<0><<<nb, kStatsThreads, 0, st>>>(a);
+    else icp_partial_kernel<1><<<nb, kStatsThreads, 0, st>>>(a);
+    if ((rc = check_launch("cn_icp_accumulate"))) return rc;
+    icp_final_kernel<<<1, kStatsThreads, 0, st>>>(nb, a.part, a.out);
+    return check_launch("cn_icp_accumulate");
 }

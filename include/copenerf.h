@@ -1104,6 +1104,62 @@ size_t cn_cloud_normal_stats_workspace_bytes(int64_t Q);
 int cn_cloud_normal_stats(const cn_cloud_normal_stats_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * ICP registration of a cloud to a target cloud (additive to ABI v22): what the
+ * Tanks-and-Temples protocol refines the trajectory alignment with.  The device does the
+ * passes of an iteration -- cn_cloud_transform, then cn_nn_grid_build / cn_nn_query over the
+ * moved cloud for the correspondences, then cn_icp_accumulate; the closed-form solve of 32
+ * doubles is the host's (copenerf.metrics.icp_register).  A correspondence kernel fused with
+ * the transform was measured slower than that composition and is not kept.
+ *
+ * A similarity is `matrix`, 12 floats (HOST values): row-major 3 x 4, s R in the left 3 x 3
+ * and t in the last column.  One device function applies it everywhere, row (a, b, c, t) as
+ *   p'_r = fmaf(c, z, fmaf(b, y, fmaf(a, x, t)))
+ * so the same point under the same matrix is the same three floats in both entries below:
+ * the sums are over the very points the search saw.  A non-finite matrix entry is CN_ERR_SHAPE.
+ *
+ * cn_cloud_transform: out [N][3] = the transform of points [N][3], one thread per point (out
+ * may be points).
+ *
+ * cn_icp_accumulate: out (DEVICE double [32]) = the sums over the pairs (i, index[i]) (index:
+ * cn_nn_query's over cn_cloud_transform's output, -1 where no target is within reach) with
+ * 0 <= index[i] < N (any other index is no pair: nothing is gathered), walked in the source's
+ * order in cn_cloud_stats' fixed two-launch tree (the same blocks rule): bitwise repeatable,
+ * and independent of the grid's within-cell order.  p' is recomputed by the shared transform,
+ * q = targets[index[i]]; every term is formed in double from the fp32 p', q and unit normal,
+ * relative to pivot c (HOST doubles, finite; the target box's centre keeps the covariance
+ * from cancelling far from the origin).
+ *   mode 0 (point-to-point):  [0] n   [1] sum |p' - q|^2   [2..4] sum (p' - c)
+ *     [5..7] sum (q - c)   [8..16] sum (q - c)(p' - c)^T, row-major (row: q's axis)
+ *     [17] sum |p' - c|^2   [18..31] 0
+ *   mode 1 (point-to-plane; n^ = target_normals[index[i]] normalised in fp32 as
+ *     cn_cloud_normal_stats does, a pair with a zero or non-finite normal is left out):
+ *     [0] n   [1] sum |p' - q|^2   [2] sum r^2, r = (p' - q) . n^
+ *     [3..23] the upper triangle of sum J^T J row by row ((0,0) (0,1) .. (0,5) (1,1) .. (5,5)),
+ *     J = [(p' - c) x n^, n^]   [24..29] sum J^T r   [30] the pairs left out   [31] 0
+ * Q = 0 or N = 0: all zeros.  Workspace (256-byte aligned): 256 blocks bytes.
+ * ------------------------------------------------------------------------ */
+typedef struct cn_cloud_transform_desc {
+    int64_t N;
+    const float* points;                /* [N][3] */
+    float matrix[12];
+    float* out;                         /* [N][3] */
+} cn_cloud_transform_desc;
+int cn_cloud_transform(const cn_cloud_transform_desc* d, cn_stream_t stream);
+typedef struct cn_icp_accumulate_desc {
+    int64_t Q, N;
+    const float* source;                /* [Q][3] */
+    const float* targets;               /* [N][3] */
+    const float* target_normals;        /* [N][3]; mode 1 only */
+    const int32_t* index;               /* [Q] */
+    float matrix[12];
+    int32_t mode;
+    double pivot[3];
+    double* out;                        /* device [32] */
+} cn_icp_accumulate_desc;
+size_t cn_icp_accumulate_workspace_bytes(int64_t Q);
+int cn_icp_accumulate(const cn_icp_accumulate_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * Mesh depth rendering and visibility (additive to ABI v22): what the ScanNet / DTU /
  * Tanks-and-Temples protocols cull a predicted mesh with before they measure it.  The
  * reference has no rasteriser; the yardstick is a float64 restatement.  A camera is a 3 x 4

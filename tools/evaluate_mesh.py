@@ -6,6 +6,8 @@ precision / recall / F-score at a threshold in the Tanks and Temples style (metr
         [--cull-views K.npy W2C.npy [SCALE.npy] --cull-resolution H W [--cull-min-views N] [--cull-tol-abs A]
          [--cull-tol-rel R] [--cull-gt]] [--depths-out DIR] [--normal-maps-out DIR] [--culled-out MESH.ply]
         [--normals] [--gt-mesh-samples S] [--out results.txt]
+        [--icp D [D ...] [--icp-mode point|plane] [--icp-scale] [--icp-samples S] [--icp-stride K [K ...]]
+         [--icp-max-iters N] [--icp-tol E] [--transform-out T.npy]]
 
 MESH.ply is a triangle mesh (tools/extract_mesh.py's output as it is), GT.ply a point cloud (a mesh's vertices are
 taken as the cloud).  --transform is a 4 x 4 similarity applied to the mesh first.  --align-poses takes two
@@ -21,7 +23,12 @@ mesh, --normal-maps-out the mesh's camera-frame normal map from every view as DI
 (mesh.render_mesh: the picture tools/render_views.py writes for the model).  --normals adds the normal consistency
 (normal_accuracy, normal_completeness, normal_consistency, n_pred_normal, n_gt_normal, after the other entries)
 against GT.ply's normals; the file must hold them.  --gt-mesh-samples S: GT.ply is a mesh; S points drawn uniformly
-by area on it (seed + 1) and their face normals are the ground-truth cloud.  Prints one `name: value` line per
+by area on it (seed + 1) and their face normals are the ground-truth cloud.  --icp refines the alignment by ICP
+before the mesh is measured (metrics.icp_register_stages, as the Tanks-and-Temples protocol follows its trajectory
+alignment): one correspondence distance per stage, coarse to fine, on --icp-samples points drawn from the mesh
+(default 200000), every --icp-stride'th of them (one K for all stages or one per stage); --icp-mode plane takes its
+normals where --normals does (and so implies it), --icp-scale also fits a scale (point mode).  The icp_* entries and the composed
+transform follow the other entries; --transform-out saves the composed 4 x 4 (float64 .npy).  Prints one `name: value` line per
 metric and with --out writes them in metrics.write_results' format."""
 import argparse
 import os
@@ -118,7 +125,24 @@ def parse_args(argv=None):
     ap.add_argument("--gt-mesh-samples", type=int)
     ap.add_argument("--culled-out")
     ap.add_argument("--out")
+    ap.add_argument("--icp", type=float, nargs="+", metavar="D")
+    ap.add_argument("--icp-mode", choices=("point", "plane"), default="point")
+    ap.add_argument("--icp-scale", action="store_true")
+    ap.add_argument("--icp-samples", type=int, default=200000)
+    ap.add_argument("--icp-stride", type=int, nargs="+", metavar="K")
+    ap.add_argument("--icp-max-iters", type=int, default=50)
+    ap.add_argument("--icp-tol", type=float, default=1e-6)
+    ap.add_argument("--transform-out")
     a = ap.parse_args(argv)
+    if a.icp is None and (a.icp_stride is not None or a.icp_scale or a.transform_out or a.icp_mode != "point"):
+        ap.error("--icp-mode, --icp-scale, --icp-stride and --transform-out need --icp")
+    if a.icp is not None:
+        if min(a.icp) <= 0 or a.icp_samples < 1 or a.icp_max_iters < 1:
+            ap.error("--icp takes positive distances, --icp-samples and --icp-max-iters positive counts")
+        if a.icp_stride is not None and (len(a.icp_stride) not in (1, len(a.icp)) or min(a.icp_stride) < 1):
+            ap.error("--icp-stride takes one positive K, or one per --icp stage")
+        if a.icp_scale and a.icp_mode == "plane":
+            ap.error("--icp-scale needs --icp-mode point")
     if a.cull_views is not None and len(a.cull_views) not in (2, 3):
         ap.error("--cull-views takes K.npy W2C.npy [SCALE.npy]")
     if (a.cull_views is None) != (a.cull_resolution is None):
@@ -132,6 +156,16 @@ def parse_args(argv=None):
     return a
 
 
+def icp_kwargs(a):
+    """The `icp` dict mesh_geometry_metrics takes, from the parsed --icp options (None without --icp)."""
+    if a.icp is None:
+        return None
+    strides = a.icp_stride or [1]
+    strides = strides * len(a.icp) if len(strides) == 1 else strides
+    return dict(stages=[dict(max_corr_dist=d, stride=k) for d, k in zip(a.icp, strides)], n_samples=a.icp_samples,
+                mode=a.icp_mode, with_scale=a.icp_scale, max_iters=a.icp_max_iters, tol=a.icp_tol)
+
+
 def main(argv=None):
     a = parse_args(argv)
     if not torch.cuda.is_available():
@@ -141,7 +175,8 @@ def main(argv=None):
     vertices, triangles, _, _ = read_ply(a.mesh)
     if triangles is None:
         raise SystemExit(f"evaluate_mesh: {a.mesh} has no faces")
-    gt, gt_triangles, gt_normals = load_ground_truth(a.gt, a.normals, a.gt_mesh_samples)
+    want_normals = a.normals or (a.icp is not None and a.icp_mode == "plane")
+    gt, gt_triangles, gt_normals = load_ground_truth(a.gt, want_normals, a.gt_mesh_samples)
     transform = None
     if a.transform:
         transform = np.load(a.transform)
@@ -174,14 +209,18 @@ def main(argv=None):
     gt_points = torch.from_numpy(gt).to(dev)
     if a.gt_mesh_samples is not None:
         gt_points, sampled_normals = sample_ground_truth(gt, gt_triangles, a.gt_mesh_samples, a.seed + 1, dev)
-        gt_normals = sampled_normals if a.normals else None
+        gt_normals = sampled_normals if want_normals else None
     elif gt_normals is not None:
         gt_normals = torch.from_numpy(np.ascontiguousarray(gt_normals)).to(dev)
     if gt_normals is not None:
         cull["gt_normals"] = gt_normals
+    if a.icp is not None:
+        cull["icp"] = icp_kwargs(a)
     result = metrics.mesh_geometry_metrics(
         tv, tf, gt_points, threshold=a.threshold, max_dist=a.max_dist, n_samples=a.samples,
         density=a.density, seed=a.seed, transform=transform, crop_min=a.crop_min, crop_max=a.crop_max, **cull)
+    if a.transform_out:
+        np.save(a.transform_out, np.asarray(result["transform"], dtype=np.float64))
     for key, value in result.items():
         print(f"{key}: {value}")
     if a.out:
