@@ -203,6 +203,38 @@ class NnQueryDesc(ctypes.Structure):
     ]
 
 
+class KnnQueryDesc(ctypes.Structure):
+    _fields_ = [
+        ("grid", ctypes.POINTER(NnGridDesc)), ("Q", c_i64), ("queries", c_ptr), ("query_records", c_i32),
+        ("max_dist", c_f32), ("k", c_i32), ("exclude_self", c_i32), ("dist", c_ptr), ("index", c_ptr), ("count", c_ptr),
+    ]
+
+
+class VoxelKeysDesc(ctypes.Structure):
+    _fields_ = [
+        ("N", c_i64), ("points", c_ptr), ("origin", c_f32 * 3), ("voxel", c_f32), ("keys", c_ptr), ("valid", c_ptr),
+    ]
+
+
+class VoxelReduceDesc(ctypes.Structure):
+    _fields_ = [
+        ("N", c_i64), ("keys", c_ptr), ("order", c_ptr), ("points", c_ptr), ("normals", c_ptr), ("colors", c_ptr),
+        ("out_points", c_ptr), ("out_normals", c_ptr), ("out_colors", c_ptr), ("out_keys", c_ptr), ("out_counts", c_ptr),
+        ("totals", c_ptr),
+    ]
+
+
+class CloudNormalsDesc(ctypes.Structure):
+    _fields_ = [
+        ("N", c_i64), ("points", c_ptr), ("index", c_ptr), ("k", c_i32), ("orient", c_i32), ("orient_to", c_f32 * 3),
+        ("normals", c_ptr), ("variation", c_ptr),
+    ]
+
+
+class KnnMeanStatsDesc(ctypes.Structure):
+    _fields_ = [("N", c_i64), ("k", c_i32), ("dist", c_ptr), ("index", c_ptr), ("mean", c_ptr), ("out", c_ptr)]
+
+
 class CloudStatsDesc(ctypes.Structure):
     _fields_ = [
         ("Q", c_i64), ("dist", c_ptr), ("points", c_ptr), ("crop_min", c_f32 * 3), ("crop_max", c_f32 * 3),
@@ -384,6 +416,13 @@ SIGNATURES = {
     "cn_nn_grid_workspace_bytes": (ctypes.c_size_t, [c_i64, c_i64]),
     "cn_nn_grid_build": (c_i32, [ctypes.POINTER(NnGridDesc), c_ptr, c_i64, c_ptr]),
     "cn_nn_query": (c_i32, [ctypes.POINTER(NnQueryDesc), c_ptr]),
+    "cn_knn_query": (c_i32, [ctypes.POINTER(KnnQueryDesc), c_ptr]),
+    "cn_voxel_keys": (c_i32, [ctypes.POINTER(VoxelKeysDesc), c_ptr]),
+    "cn_voxel_reduce_workspace_bytes": (ctypes.c_size_t, [c_i64]),
+    "cn_voxel_reduce": (c_i32, [ctypes.POINTER(VoxelReduceDesc), c_ptr, c_i64, c_ptr]),
+    "cn_cloud_normals": (c_i32, [ctypes.POINTER(CloudNormalsDesc), c_ptr]),
+    "cn_knn_mean_stats_workspace_bytes": (ctypes.c_size_t, [c_i64]),
+    "cn_knn_mean_stats": (c_i32, [ctypes.POINTER(KnnMeanStatsDesc), c_ptr, c_i64, c_ptr]),
     "cn_cloud_stats_workspace_bytes": (ctypes.c_size_t, [c_i64]),
     "cn_cloud_stats": (c_i32, [ctypes.POINTER(CloudStatsDesc), c_ptr, c_i64, c_ptr]),
     "cn_cloud_normal_stats_workspace_bytes": (ctypes.c_size_t, [c_i64]),

@@ -493,6 +493,94 @@ def nearest_distances(queries, targets, max_dist=math.inf, cell=None, sort_queri
     return ops.nn_query(grid, queries, max_dist)
 
 
+def knn(queries, targets, k, max_dist=math.inf, exclude_self=False):
+    """(dist fp32 [Q, k], index int32 [Q, k]): for every query its k nearest targets (1 <= k <= 32), exact, each row
+    ascending under (distance, index) and padded with (max_dist, -1) where fewer than k targets are nearer than
+    max_dist (cn_knn_query on nearest_distances' grid, the queries binned through it).  exclude_self: queries is
+    targets, and no point is its own neighbour (exact duplicates at other indices still are)."""
+    ops._need_cloud("knn", queries, "queries")
+    ops._need_cloud("knn", targets, "targets")
+    if queries.device != targets.device:
+        raise RuntimeError("knn: queries and targets on different devices")
+    k = int(k)
+    if not 1 <= k <= ops.KNN_MAX_K:
+        raise ValueError(f"knn: k {k} (in [1, {ops.KNN_MAX_K}])")
+    N, Q = targets.shape[0], queries.shape[0]
+    if exclude_self and Q != N:
+        raise ValueError(f"knn: exclude_self with {Q} queries of {N} targets")
+    if N == 0 or Q == 0:
+        return (torch.full((Q, k), float(max_dist), dtype=torch.float32, device=queries.device),
+                torch.full((Q, k), -1, dtype=torch.int32, device=queries.device))
+    box = torch.stack([targets.amin(0), targets.amax(0)]).tolist()
+    if not all(math.isfinite(x) for x in box[0] + box[1]):
+        raise ValueError("knn: targets must be finite")
+    cell, dims = nn_cell_size(box[0], box[1], N)
+    grid = ops.nn_grid(targets, box[0], cell, dims)
+    binned = grid if queries is targets else ops.nn_grid(queries, box[0], cell, dims)
+    dist, index, _ = ops.knn_query(grid, binned.sorted, k, max_dist, exclude_self=exclude_self, records=True)
+    return dist, index
+
+
+def voxel_down_sample(points, voxel, normals=None, colors=None, origin=None):
+    """Voxel down-sampling as the Tanks-and-Temples protocol applies it: one point per occupied voxel of edge `voxel`,
+    the mean of the voxel's points (and of their colors fp32 [N, 3]; normals are averaged and re-normalised, a zero
+    sum staying zero), in ascending voxel-key order (cn_voxel_keys, a stable torch sort, cn_voxel_reduce; double
+    sums in ascending original index, bitwise repeatable).  origin (3 numbers) anchors the voxel lattice, by default
+    the smallest finite coordinate per axis.  Points that are not finite, or farther than 2^21 voxels from the
+    origin, are dropped and counted.  Returns a dict: points, normals, colors (None where not given), counts int32
+    [M], n_dropped."""
+    ops._need_cloud("voxel_down_sample", points, "points")
+    voxel = float(voxel)
+    if not (voxel > 0.0 and math.isfinite(voxel)):
+        raise ValueError(f"voxel_down_sample: voxel size {voxel}")
+    N = points.shape[0]
+    if origin is None:
+        finite = torch.where(torch.isfinite(points), points, torch.full_like(points, math.inf))
+        origin = finite.amin(0).tolist() if N else [0.0, 0.0, 0.0]
+        origin = [x if math.isfinite(x) else 0.0 for x in origin]
+    keys, _ = ops.voxel_keys(points, origin, voxel)
+    skeys, order = torch.sort(keys, stable=True)
+    out = ops.voxel_reduce(skeys, order, points, normals, colors)
+    M, dropped = out["totals"].tolist()
+    return {"points": out["points"][:M].contiguous(),
+            "normals": None if normals is None else out["normals"][:M].contiguous(),
+            "colors": None if colors is None else out["colors"][:M].contiguous(),
+            "counts": out["counts"][:M].contiguous(), "n_dropped": int(dropped)}
+
+
+def estimate_normals(points, k=16, max_dist=math.inf, orient_to=None, want_variation=False):
+    """Normals of a cloud without them: per point the PCA normal of its k nearest neighbours within max_dist, the
+    point itself included (knn over the cloud, cn_cloud_normals).  A point with fewer than 3 neighbours, or a
+    collinear neighbourhood, gets the zero normal, which the normal metrics and point-to-plane ICP leave out and
+    count.  orient_to: a viewpoint the normals are flipped towards; without it the sign is a convention (the largest
+    component positive) -- the normal metrics take |n . n'|, and point-to-plane ICP is sign-free.  Returns normals
+    fp32 [N, 3], or (normals, surface variation fp32 [N])."""
+    _, index = knn(points, points, k, max_dist)
+    normals, variation = ops.cloud_normals(points, index, orient_to, want_variation)
+    return (normals, variation) if want_variation else normals
+
+
+def outlier_cut(sums, std_ratio):
+    """(mu, sigma, mu + std_ratio sigma) from cn_knn_mean_stats' three sums (the population standard deviation)."""
+    n, s, s2 = (float(x) for x in sums)
+    if n < 1:
+        return 0.0, 0.0, 0.0
+    mu = s / n
+    sigma = math.sqrt(max(s2 / n - mu * mu, 0.0))
+    return mu, sigma, mu + float(std_ratio) * sigma
+
+
+def remove_statistical_outliers(points, k=20, std_ratio=2.0):
+    """The statistical outlier filter of scan pipelines: a point goes when the mean distance to its k nearest
+    neighbours (itself excluded) is above mu + std_ratio sigma of those means over the cloud.  Returns (the kept
+    points, the keep mask bool [N])."""
+    dist, index = knn(points, points, k, exclude_self=True)
+    mean, sums = ops.knn_mean_stats(dist, index)
+    _, _, cut = outlier_cut(sums.tolist(), std_ratio)
+    keep = mean <= cut
+    return points[keep].contiguous(), keep
+
+
 def _cloud_side(queries, targets, threshold, max_dist, crop_min, crop_max):
     dist, _ = nearest_distances(queries, targets, max_dist)
     return ops.cloud_stats(dist, threshold, max_dist, queries if crop_min is not None else None, crop_min, crop_max)
@@ -757,6 +845,9 @@ def _icp_refine(icp, vertices, triangles, gt_points, gt_normals, transform, n_sa
     if stages is None:
         stages = [{"max_corr_dist": icp.pop("max_corr_dist")}]
     n_reg = int(icp.pop("n_samples", 0))
+    voxel = icp.pop("voxel", None)
+    if voxel is not None and not (float(voxel) > 0.0 and math.isfinite(float(voxel))):
+        raise ValueError(f"mesh_geometry_metrics: icp voxel {voxel}")
     if n_reg < 1 or n_reg >= 2 ** 31:
         raise ValueError(f"mesh_geometry_metrics: icp n_samples {n_reg}")
     plane = icp.get("mode") == "plane" or any(st.get("mode") == "plane" for st in stages)
@@ -782,6 +873,12 @@ def _icp_refine(icp, vertices, triangles, gt_points, gt_normals, transform, n_sa
         raise ValueError(f"mesh_geometry_metrics: {S} samples")
     philox = torch.tensor([int(seed), 4 * S], dtype=torch.uint64, device=dev)
     reg, _ = ops.mesh_sample(handle, n_reg, philox)
+    if voxel is not None:
+        reg = voxel_down_sample(reg, voxel)["points"]
+        down = voxel_down_sample(gt_points, voxel, normals=gt_normals if plane else None)
+        gt_points = down["points"]
+        if plane:
+            icp["target_normals"] = down["normals"]
     res = icp_register_stages(reg, gt_points, stages, **icp)
     return res.transform @ base, res
 
@@ -796,7 +893,7 @@ def _with_icp(res, icp_res, transform):
 def mesh_geometry_metrics(vertices, triangles, gt_points, *, threshold, max_dist=math.inf, n_samples=None,
                           density=None, seed=0, transform=None, crop_min=None, crop_max=None, cull_views=None,
                           cull_resolution=None, cull_gt=False, cull_min_views=1, cull_tol_abs=None, cull_tol_rel=None,
-                          gt_normals=None, icp=None):
+                          gt_normals=None, icp=None, gt_voxel=None, gt_outliers=None, gt_estimate_normals=None):
     """Geometry metrics of a triangle mesh against a ground-truth cloud, all on the device.  vertices fp32
     [V, 3], triangles int32 [T, 3] (NeuSRenderer.extract_geometry's output as it is) and gt_points fp32 [N, 3]
     are device tensors.  The mesh is sampled uniformly by area (cn_mesh_area / cn_mesh_sample, Philox seed
@@ -831,7 +928,17 @@ def mesh_geometry_metrics(vertices, triangles, gt_points, *, threshold, max_dist
     `transform`, and everything above goes on with the refined transform.  cull_gt keeps using the initial
     transform: the ground truth is filtered before the registration that refines it.  The dict then gains
     icp_fitness, icp_rmse, icp_iterations, icp_converged and transform (the composed 4 x 4 as nested lists).
-    With icp=None nothing changes."""
+    With icp=None nothing changes.
+    Preparation of a raw ground-truth scan, all off by default and applied in this order before anything above:
+    gt_outliers=(k, ratio) removes its statistical outliers (remove_statistical_outliers; gt_normals follow the
+    mask), gt_voxel=V voxel-down-samples it (voxel_down_sample; normals are averaged), gt_estimate_normals=k gives
+    a ground truth without normals the PCA normals of its k nearest neighbours (estimate_normals; not together with
+    gt_normals), which turns the normal metrics and icp mode "plane" on.  icp's `voxel` down-samples the
+    registration samples and the ground truth the registration sees (not the evaluation's) to that voxel size."""
+    if gt_estimate_normals is not None and gt_normals is not None:
+        raise ValueError("mesh_geometry_metrics: gt_estimate_normals with gt_normals")
+    if gt_voxel is not None and not (float(gt_voxel) > 0.0 and math.isfinite(float(gt_voxel))):
+        raise ValueError(f"mesh_geometry_metrics: gt_voxel {gt_voxel}")
     if gt_normals is not None:
         ops._need_cloud("mesh_geometry_metrics", gt_normals, "gt_normals")
         if gt_normals.shape[0] != gt_points.shape[0]:
@@ -850,6 +957,16 @@ def mesh_geometry_metrics(vertices, triangles, gt_points, *, threshold, max_dist
     ops._need_cloud("mesh_geometry_metrics", triangles, "triangles", dtype=torch.int32)
     ops._need_cloud("mesh_geometry_metrics", gt_points, "gt_points")
     dev = vertices.device
+    if gt_outliers is not None:
+        k_out, ratio = gt_outliers
+        gt_points, keep = remove_statistical_outliers(gt_points, int(k_out), float(ratio))
+        if gt_normals is not None:
+            gt_normals = gt_normals[keep].contiguous()
+    if gt_voxel is not None:
+        down = voxel_down_sample(gt_points, gt_voxel, normals=gt_normals)
+        gt_points, gt_normals = down["points"], down["normals"]
+    if gt_estimate_normals is not None:
+        gt_normals = estimate_normals(gt_points, int(gt_estimate_normals))
     if cull_views is not None:
         from . import mesh
         tol = {k: v for k, v in (("tol_abs", cull_tol_abs), ("tol_rel", cull_tol_rel)) if v is not None}

@@ -1443,6 +1443,160 @@ def nn_query(grid, queries, max_dist=math.inf, want_index=True, records=False):
     return dist, index
 
 
+KNN_MAX_K = 32
+
+
+def knn_query(grid, queries, k, max_dist=math.inf, exclude_self=False, want_count=False, records=False):
+    """cn_knn_query: (dist fp32 [Q, k], index int32 [Q, k], count int32 [Q] or None), for every query the exact k
+    nearest points of `grid`, each row ascending under (squared distance, original index) and padded with
+    (max_dist, -1) where fewer than k points are nearer than max_dist.  queries as in nn_query (records=True: the
+    `sorted` records of an nn_grid over the queries).  exclude_self leaves out the target whose original index is the
+    query's own; it needs as many queries as the grid has points."""
+    _need_cloud("knn_query", queries, "queries", cols=4 if records else 3)
+    if queries.device != grid.sorted.device:
+        raise RuntimeError("knn_query: queries and grid on different devices")
+    k = int(k)
+    if not 1 <= k <= KNN_MAX_K:
+        raise RuntimeError(f"knn_query: k {k} (in [1, {KNN_MAX_K}])")
+    dev = queries.device
+    Q = queries.shape[0]
+    if exclude_self and Q != grid.desc.N:
+        raise RuntimeError(f"knn_query: exclude_self with {Q} queries of {grid.desc.N} targets")
+    dist = torch.empty(Q, k, dtype=torch.float32, device=dev)
+    index = torch.empty(Q, k, dtype=torch.int32, device=dev)
+    count = torch.empty(Q, dtype=torch.int32, device=dev) if want_count else None
+    d = _lib.KnnQueryDesc()
+    d.grid = ctypes.pointer(grid.desc)
+    d.Q, d.queries, d.query_records, d.max_dist = Q, _ptr(queries) if Q else None, int(bool(records)), float(max_dist)
+    d.k, d.exclude_self = k, int(bool(exclude_self))
+    if Q:
+        d.dist, d.index, d.count = _ptr(dist), _ptr(index), _ptr(count) if want_count else None
+    _lib.call("cn_knn_query", ctypes.byref(d), _stream())
+    return dist, index, count
+
+
+# ---------------------------------------------------------------------------
+# Point-cloud preparation (additive to ABI v22): cn_cloud.hip
+VOXEL_KEY_NONE = (1 << 63) - 1
+VOXEL_AXIS_BITS = 21
+
+
+def voxel_keys(points, origin, voxel, want_valid=False):
+    """cn_voxel_keys: (keys int64 [N], valid int32 [N] or None), the 63-bit voxel key of every point for voxels of
+    edge `voxel` from `origin` (three 21-bit indices, x highest); VOXEL_KEY_NONE and valid 0 for a point that is
+    not finite or outside the 21-bit range."""
+    _need_cloud("voxel_keys", points, "points")
+    voxel = float(voxel)
+    if not (voxel > 0.0 and math.isfinite(voxel)):
+        raise RuntimeError(f"voxel_keys: voxel size {voxel}")
+    dev = points.device
+    N = points.shape[0]
+    keys = torch.empty(N, dtype=torch.int64, device=dev)
+    valid = torch.empty(N, dtype=torch.int32, device=dev) if want_valid else None
+    d = _lib.VoxelKeysDesc()
+    d.N, d.origin, d.voxel = N, (_lib.c_f32 * 3)(*[float(x) for x in origin]), voxel
+    if N:
+        d.points, d.keys, d.valid = _ptr(points), _ptr(keys), _ptr(valid) if want_valid else None
+    _lib.call("cn_voxel_keys", ctypes.byref(d), _stream())
+    return keys, valid
+
+
+def voxel_reduce(keys, order, points, normals=None, colors=None):
+    """cn_voxel_reduce over the keys sorted ascending by a stable sort and `order`, the original index of every
+    sorted element (torch.sort(stable=True)'s two outputs): a dict with points fp32 [N, 3] (the voxel means, the
+    first M rows written), normals / colors (where given: the re-normalised mean normal, the mean colour), counts
+    int32 [N], keys int64 [N] and totals, a device int32 [2] = (M, points dropped); the voxels are in ascending key
+    order.  The caller reads totals (one host read) and keeps the first M rows."""
+    _need_cloud("voxel_reduce", points, "points")
+    dev = points.device
+    N = points.shape[0]
+    for t, name in ((keys, "keys"), (order, "order")):
+        if t.dtype != torch.int64 or tuple(t.shape) != (N,) or not t.is_contiguous() or t.device != dev:
+            raise RuntimeError(f"voxel_reduce: {name} must be a contiguous int64 [{N}] device tensor (got {t.dtype} "
+                               f"{tuple(t.shape)})")
+    d = _lib.VoxelReduceDesc()
+    d.N = N
+    out = {"points": torch.empty(N, 3, dtype=torch.float32, device=dev), "normals": None, "colors": None,
+           "counts": torch.empty(N, dtype=torch.int32, device=dev), "keys": torch.empty(N, dtype=torch.int64, device=dev),
+           "totals": torch.empty(2, dtype=torch.int32, device=dev)}
+    for t, name in ((normals, "normals"), (colors, "colors")):
+        if t is None:
+            continue
+        _need_cloud("voxel_reduce", t, name)
+        if t.shape[0] != N or t.device != dev:
+            raise RuntimeError(f"voxel_reduce: {name} {tuple(t.shape)} for {N} points")
+        out[name] = torch.empty(N, 3, dtype=torch.float32, device=dev)
+    d.totals = _ptr(out["totals"])
+    if N:
+        d.keys, d.order, d.points = _ptr(keys), _ptr(order), _ptr(points)
+        d.out_points, d.out_counts, d.out_keys = _ptr(out["points"]), _ptr(out["counts"]), _ptr(out["keys"])
+        if normals is not None:
+            d.normals, d.out_normals = _ptr(normals), _ptr(out["normals"])
+        if colors is not None:
+            d.colors, d.out_colors = _ptr(colors), _ptr(out["colors"])
+    lib = _lib.load()
+    ws = _workspace(lib.cn_voxel_reduce_workspace_bytes(N), dev)
+    _lib.check(lib.cn_voxel_reduce(ctypes.byref(d), _ptr(ws), ws.numel(), _stream()), "cn_voxel_reduce")
+    return out
+
+
+def _need_rows(fn, t, name, N, k, dtype):
+    _need(t, name, ndim=0)
+    if t.dtype != dtype or t.dim() != 2 or t.shape[0] != N or not 1 <= t.shape[1] <= KNN_MAX_K or not t.is_contiguous():
+        raise RuntimeError(f"{fn}: {name} must be a contiguous {dtype} [{N}, k] device tensor with k in [1, {KNN_MAX_K}] "
+                           f"(got {t.dtype}, shape {tuple(t.shape)})")
+    if k is not None and t.shape[1] != k:
+        raise RuntimeError(f"{fn}: {name} has {t.shape[1]} columns, {k} expected")
+
+
+def cloud_normals(points, index, orient_to=None, want_variation=False):
+    """cn_cloud_normals: (normals fp32 [N, 3], variation fp32 [N] or None) from every point's neighbour row index
+    int32 [N, k] (knn_query's over the cloud itself): the unit eigenvector of the smallest eigenvalue of the
+    neighbours' covariance, and the surface variation l0 / (l0 + l1 + l2).  Zero for fewer than 3 valid neighbours,
+    non-finite input or a collinear neighbourhood.  orient_to (3 numbers): flipped towards that point; without it
+    the component of largest magnitude is positive."""
+    _need_cloud("cloud_normals", points, "points")
+    N = points.shape[0]
+    _need_rows("cloud_normals", index, "index", N, None, torch.int32)
+    dev = points.device
+    if index.device != dev:
+        raise RuntimeError("cloud_normals: tensors on different devices")
+    normals = torch.empty(N, 3, dtype=torch.float32, device=dev)
+    variation = torch.empty(N, dtype=torch.float32, device=dev) if want_variation else None
+    d = _lib.CloudNormalsDesc()
+    d.N, d.k = N, index.shape[1]
+    if orient_to is not None:
+        d.orient, d.orient_to = 1, (_lib.c_f32 * 3)(*[float(x) for x in orient_to])
+    if N:
+        d.points, d.index, d.normals = _ptr(points), _ptr(index), _ptr(normals)
+        d.variation = _ptr(variation) if want_variation else None
+    _lib.call("cn_cloud_normals", ctypes.byref(d), _stream())
+    return normals, variation
+
+
+def knn_mean_stats(dist, index):
+    """cn_knn_mean_stats: (mean fp32 [N], a device double [3] = (rows with a finite mean, the sum of those means,
+    the sum of their squares)) over knn_query's dist fp32 [N, k] / index int32 [N, k]: per row the mean of the
+    distances whose index is not -1 (+inf for a row without one)."""
+    _need(dist, "dist", ndim=0)
+    N = dist.shape[0] if dist.dim() == 2 else -1
+    _need_rows("knn_mean_stats", dist, "dist", N, None, torch.float32)
+    _need_rows("knn_mean_stats", index, "index", N, dist.shape[1], torch.int32)
+    dev = dist.device
+    if index.device != dev:
+        raise RuntimeError("knn_mean_stats: tensors on different devices")
+    mean = torch.empty(N, dtype=torch.float32, device=dev)
+    out = torch.empty(3, dtype=torch.float64, device=dev)
+    d = _lib.KnnMeanStatsDesc()
+    d.N, d.k, d.out = N, dist.shape[1], _ptr(out)
+    if N:
+        d.dist, d.index, d.mean = _ptr(dist), _ptr(index), _ptr(mean)
+    lib = _lib.load()
+    ws = _workspace(lib.cn_knn_mean_stats_workspace_bytes(N), dev)
+    _lib.check(lib.cn_knn_mean_stats(ctypes.byref(d), _ptr(ws), ws.numel(), _stream()), "cn_knn_mean_stats")
+    return mean, out
+
+
 def cloud_stats(dist, threshold, max_dist=math.inf, points=None, crop_min=None, crop_max=None):
     """cn_cloud_stats: a device double [4] = (points inside the crop box, those with dist < max_dist, the sum of
     their distances, those of them with dist < threshold) over dist fp32 [Q]; points fp32 [Q, 3] with crop_min /

@@ -124,6 +124,31 @@ __device__ __forceinline__ int block_excl_scan(int x, int* total) {
     return before + incl - x;
 }
 
+// The fixed-order double reductions of the cloud statistics (cn_mesh_eval.hip, cn_cloud.hip): launch 1 of
+// stats_blocks(Q) blocks of 256 threads, thread t of block b taking elements (b 256 + t) + j (blocks 256), a fixed
+// tree per block; launch 2 of one block over the block partials.
+constexpr int kStatsThreads = 256;
+constexpr int kStatsMaxBlocks = 1024;
+
+inline int stats_blocks(int64_t Q) {
+    int64_t b = (Q + 1023) / 1024;
+    return (int)(b < 1 ? 1 : (b > kStatsMaxBlocks ? kStatsMaxBlocks : b));
+}
+
+// the sum over the block of one value per thread, in a fixed tree; valid in thread 0
+__device__ __forceinline__ double block_sum_fixed(double x, double* sh) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x = x + __shfl_down(x, off, kWave);
+    __syncthreads();  // (a previous call's readers are done)
+    if (lane == 0) sh[w] = x;
+    __syncthreads();
+    double s = 0.0;
+    if (threadIdx.x == 0)
+        for (int i = 0; i < kStatsThreads / kWave; ++i) s = s + sh[i];
+    return s;
+}
+
 // grid_sample's border clip of an unnormalised coordinate (GridSampler.h clip_coordinates_set_grad):
 // the clamped coordinate, *mult = 0 where it was clamped (the borders count as clamped).  Shared by the
 // two bilinear warps (cn_refine.hip, cn_flow_rgb.hip).

@@ -5,6 +5,8 @@
 // ICP registration of a cloud to the targets of such a grid sits on the same search: a similarity applied by one
 // device function (cn_cloud_transform; the correspondences are cn_nn_query over its output) and the reduction of the
 // pairs into the 32 sums of a closed-form step (cn_icp_accumulate); the yardstick is tests/icp_ref.py.
+// The exact k nearest neighbours on the same grid (cn_knn_query, the k-best list in LDS) feed the point-cloud
+// preparation passes of cn_cloud.hip; the yardstick is tests/cloud_ref.py.
 //
 // Determinism.  The area scan is a nest of SEQUENTIAL sums, not a tree: a thread sums its 4 triangles in order,
 // a wave its 64 threads in lane order, a tile its 4 waves in order, and one wave the tile totals in order; every
@@ -478,15 +480,156 @@ __global__ void __launch_bounds__(256) nn_query_kernel(QueryArgs a) {
     if (a.index) a.index[out] = found ? bi : -1;
 }
 
-// ---- statistics -----------------------------------------------------------------------------------------
+// ---- the k nearest neighbours ------------------------------------------------------------------------------
 
-constexpr int kStatsThreads = 256;
-constexpr int kStatsMaxBlocks = 1024;
+struct KnnArgs {
+    QueryArgs q;  // dist / index are [Q][k]
+    int k;
+    int exclude_self;
+    int32_t* count;
+};
 
-int stats_blocks(int64_t Q) {
-    int64_t b = (Q + 1023) / 1024;
-    return (int)(b < 1 ? 1 : (b > kStatsMaxBlocks ? kStatsMaxBlocks : b));
+// A lane's k-best list lives in LDS as [slot][lane]: slot j of lane t is word j 256 + t of each array, so whatever
+// slots the lanes of a wave are at, lane t is in bank t mod 64 -- no conflicts, and no runtime-indexed private array
+// (which would go to scratch).  Slots 0 .. n - 1 are ascending under (squared distance, original index).
+template <int K>
+struct KnnList {
+    float (*d)[256];
+    int (*i)[256];
+    int t, k;
+    int n;     // slots in use, <= k
+    float wd;  // the current worst pair once the list is full; (inf, -1) before: any finite distance enters, and
+    int wi;    // an infinite or NaN one never does -- nn_query_kernel's (best, bi) start
+};
+
+// The records [s, e) against the list: a record enters when its pair is below the worst pair (one compare for one
+// that cannot), by an insertion that shifts the larger pairs up one slot.
+template <int K>
+__device__ __forceinline__ void knn_scan_records(const KnnArgs& a, int s, int e, float qx, float qy, float qz, int self,
+                                                 KnnList<K>& L) {
+    s = s < 0 ? 0 : s;
+    e = (int64_t)e > a.q.N ? (int)a.q.N : e;  // (cell_start is the build's: the clamps only bound a foreign array)
+    for (int j = s; j < e; ++j) {             // bound: e - s <= N records
+        const floatx4 r = a.q.sorted[j];      // one 16-byte load per record
+        const float dx = r[0] - qx, dy = r[1] - qy, dz = r[2] - qz;
+        const float d2 = (dx * dx + dy * dy) + dz * dz;  // scan_records' expression
+        const int idx = __float_as_int(r[3]);
+        if (!(d2 < L.wd || (d2 == L.wd && idx < L.wi))) continue;
+        if (a.exclude_self && idx == self) continue;
+        int p = L.n < L.k ? L.n : L.k - 1;  // the slot that opens: a new one, or the worst pair's
+        for (int m = 1; m < K && p > 0; ++m) {  // bound: K - 1 shifts
+            const float pd = L.d[p - 1][L.t];
+            const int pi = L.i[p - 1][L.t];
+            if (pd < d2 || (pd == d2 && pi < idx)) break;
+            L.d[p][L.t] = pd;
+            L.i[p][L.t] = pi;
+            --p;
+        }
+        L.d[p][L.t] = d2;
+        L.i[p][L.t] = idx;
+        if (L.n < L.k) ++L.n;
+        if (L.n == L.k) {
+            L.wd = L.d[L.k - 1][L.t];
+            L.wi = L.i[L.k - 1][L.t];
+        }
+    }
 }
+
+// One lane per query, nn_query_kernel's shells with the k-th best pair in place of the best.  After shells 0 .. s
+// every unvisited target lies, by the argument above nn_query_kernel, at a true distance above lb (by more than the
+// fp32 distance arithmetic can lose), so its squared distance as this kernel forms it is >= lb^2.  The list holds
+// the k smallest pairs among the visited targets (an insertion only ever drops the largest of k + 1), and:
+//   list full and worst < lb^2  =>  every unvisited target's pair is above the list's worst pair: none of them is
+//     among the k smallest pairs of all targets, so the list is final;
+//   lb >= max_dist  =>  no unvisited target is within max_dist; those of the list that are stay its prefix;
+//   no side with cells left  =>  every cell has been visited.
+// A list that is not full has worst = +inf and never stops on the first rule.  Rows are cut at max_dist when they
+// are written: sqrtf never falls, so the pairs with sqrtf(d^2) < max_dist are a prefix of the ascending list, and
+// the k smallest pairs of all targets cut there are the k smallest among the targets within max_dist.
+// exclude_self leaves out the one target whose original index is the query's own (the lane's position, or its
+// record's index): the argument is the same over the remaining targets.  K is the capacity (k <= K); the LDS is
+// 256 lanes x K slots x 8 bytes.
+template <int K>
+__global__ void __launch_bounds__(256) knn_query_kernel(KnnArgs a) {
+    __shared__ float sd[K][256];
+    __shared__ int si[K][256];
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.q.Q) return;  // (no barrier below: a lane only ever touches its own column of the LDS)
+    float q[3];
+    int64_t out = i;
+    if (a.q.records) {
+        const floatx4 r = reinterpret_cast<const floatx4*>(a.q.q)[i];
+        q[0] = r[0];
+        q[1] = r[1];
+        q[2] = r[2];
+        out = __float_as_int(r[3]);
+        if (out < 0 || out >= a.q.Q) return;  // (never for cn_nn_grid_build's records)
+    } else {
+        q[0] = a.q.q[i * 3];
+        q[1] = a.q.q[i * 3 + 1];
+        q[2] = a.q.q[i * 3 + 2];
+    }
+    const Grid& g = a.q.g;
+    int c[3];
+    float slack = 0.0f;
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+        c[ax] = axis_cell(q[ax], g.o[ax], g.cell, g.d[ax]);
+        slack = fmaxf(slack, (fabsf(g.o[ax]) + fabsf(q[ax]) + (float)g.d[ax] * g.cell) * (1.0f / 1048576.0f));
+    }
+    const int ny = g.d[1], nz = g.d[2];
+    KnnList<K> L{sd, si, (int)threadIdx.x, a.k, 0, INFINITY, -1};
+    const int self = (int)out;
+    // bound: the grid's largest dimension -- shell maxdim - 1 around any cell holds every cell of the grid
+    for (int s = 0; s < a.q.maxdim; ++s) {
+        const int x0 = max(c[0] - s, 0), x1 = min(c[0] + s, g.d[0] - 1);
+        const int y0 = max(c[1] - s, 0), y1 = min(c[1] + s, ny - 1);
+        const int z0 = max(c[2] - s, 0), z1 = min(c[2] + s, nz - 1);
+        for (int x = x0; x <= x1; ++x) {      // bound: 2 s + 1
+            for (int y = y0; y <= y1; ++y) {  // bound: 2 s + 1
+                const int row = (x * ny + y) * nz;
+                if (abs(x - c[0]) == s || abs(y - c[1]) == s) {
+                    // a face row of the shell: its cells z0 .. z1 are one run of records (z is the fastest index)
+                    knn_scan_records<K>(a, a.q.start[row + z0], a.q.start[row + z1 + 1], q[0], q[1], q[2], self, L);
+                } else {
+                    // an inner row: the two end cells, where they are inside the grid
+                    const int za = c[2] - s, zb = c[2] + s;
+                    if (za >= 0)
+                        knn_scan_records<K>(a, a.q.start[row + za], a.q.start[row + za + 1], q[0], q[1], q[2], self, L);
+                    if (zb < nz)
+                        knn_scan_records<K>(a, a.q.start[row + zb], a.q.start[row + zb + 1], q[0], q[1], q[2], self, L);
+                }
+            }
+        }
+        float lb = INFINITY;
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) {
+            if (c[ax] + s + 1 <= g.d[ax] - 1) lb = fminf(lb, (g.o[ax] + (float)(c[ax] + s + 1) * g.cell) - q[ax]);
+            if (c[ax] - s - 1 >= 0) lb = fminf(lb, q[ax] - (g.o[ax] + (float)(c[ax] - s) * g.cell));
+        }
+        if (lb == INFINITY) break;  // the shell left the grid on every side
+        lb = (lb - slack) * (1.0f - 1.0f / 1048576.0f);
+        if (lb > 0.0f && (L.wd < lb * lb || lb >= a.q.max_dist)) break;
+    }
+    int found = 0;
+    for (int j = 0; j < a.k; ++j) {  // bound: k <= K slots
+        float d = a.q.max_dist;
+        int idx = -1;
+        if (j < L.n) {
+            const float dj = sqrtf(sd[j][threadIdx.x]);
+            if (dj < a.q.max_dist) {
+                d = dj;
+                idx = si[j][threadIdx.x];
+                ++found;
+            }
+        }
+        a.q.dist[out * a.k + j] = d;
+        a.q.index[out * a.k + j] = idx;
+    }
+    if (a.count) a.count[out] = found;
+}
+
+// ---- statistics -----------------------------------------------------------------------------------------
 
 struct StatsArgs {
     int64_t Q;
@@ -497,20 +640,6 @@ struct StatsArgs {
     double* part;  // [blocks][4]
     double* out;   // [4]
 };
-
-// the sum over the block of one value per thread, in a fixed tree; valid in thread 0
-__device__ __forceinline__ double block_sum_fixed(double x, double* sh) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x = x + __shfl_down(x, off, kWave);
-    __syncthreads();  // (a previous call's readers are done)
-    if (lane == 0) sh[w] = x;
-    __syncthreads();
-    double s = 0.0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < kStatsThreads / kWave; ++i) s = s + sh[i];
-    return s;
-}
 
 // launch 1: thread t of block b takes elements (b 256 + t) + j (blocks 256), j ascending
 __global__ void __launch_bounds__(kStatsThreads) stats_partial_kernel(StatsArgs a) {
@@ -887,6 +1016,51 @@ extern "C" int cn_nn_query(const cn_nn_query_desc* d, cn_stream_t stream) {
     a.maxdim = a.maxdim > a.g.d[2] ? a.maxdim : a.g.d[2];
     nn_query_kernel<<<(unsigned)((d->Q + 255) / 256), 256, 0, (hipStream_t)stream>>>(a);
     return check_launch("cn_nn_query");
+}
+
+extern "C" int cn_knn_query(const cn_knn_query_desc* d, cn_stream_t stream) {
+    CN_REQUIRE(d, CN_ERR_ARG, "cn_knn_query: null descriptor");
+    int64_t ncells;
+    int rc = grid_check("cn_knn_query", d->grid, &ncells);
+    if (rc) return rc;
+    CN_REQUIRE(d->Q >= 0 && d->Q <= kMaxCount, CN_ERR_SHAPE, "cn_knn_query: Q %lld (in [0, 2^31))", (long long)d->Q);
+    CN_REQUIRE(d->k >= 1 && d->k <= 32, CN_ERR_SHAPE, "cn_knn_query: k %d (in [1, 32])", d->k);
+    CN_REQUIRE(d->query_records == 0 || d->query_records == 1, CN_ERR_ARG, "cn_knn_query: query_records %d",
+               d->query_records);
+    CN_REQUIRE(d->exclude_self == 0 || d->exclude_self == 1, CN_ERR_ARG, "cn_knn_query: exclude_self %d", d->exclude_self);
+    CN_REQUIRE(!d->exclude_self || d->Q == d->grid->N, CN_ERR_SHAPE,
+               "cn_knn_query: exclude_self with Q %lld queries of N %lld targets (a self-query has Q = N)", (long long)d->Q,
+               (long long)d->grid->N);
+    CN_REQUIRE(!(d->max_dist != d->max_dist) && d->max_dist >= 0.0f, CN_ERR_SHAPE, "cn_knn_query: max_dist %g",
+               (double)d->max_dist);
+    if (d->Q == 0) return CN_OK;
+    CN_REQUIRE(d->queries && d->dist && d->index, CN_ERR_ARG, "cn_knn_query: null queries / dist / index");
+    CN_REQUIRE(((uintptr_t)d->queries & (d->query_records ? 15 : 3)) == 0 && ((uintptr_t)d->dist & 3) == 0 &&
+                   ((uintptr_t)d->index & 3) == 0 && ((uintptr_t)d->count & 3) == 0,
+               CN_ERR_ALIGN, "cn_knn_query: queries %d-byte, dist / index / count 4-byte aligned", d->query_records ? 16 : 4);
+    KnnArgs a{};
+    a.q.g = grid_of(d->grid);
+    a.q.N = d->grid->N;
+    a.q.Q = d->Q;
+    a.q.q = d->queries;
+    a.q.records = d->query_records;
+    a.q.sorted = reinterpret_cast<const floatx4*>(d->grid->sorted);
+    a.q.start = d->grid->cell_start;
+    a.q.max_dist = d->max_dist;
+    a.q.dist = d->dist;
+    a.q.index = d->index;
+    a.q.maxdim = a.q.g.d[0] > a.q.g.d[1] ? a.q.g.d[0] : a.q.g.d[1];
+    a.q.maxdim = a.q.maxdim > a.q.g.d[2] ? a.q.maxdim : a.q.g.d[2];
+    a.k = d->k;
+    a.exclude_self = d->exclude_self;
+    a.count = d->count;
+    const unsigned blocks = (unsigned)((d->Q + 255) / 256);
+    hipStream_t st = (hipStream_t)stream;
+    // the smallest capacity that holds k: 16, 32 or 64 KB of LDS per block
+    if (d->k <= 8) knn_query_kernel<8><<<blocks, 256, 0, st>>>(a);
+    else if (d->k <= 16) knn_query_kernel<16><<<blocks, 256, 0, st>>>(a);
+    else knn_query_kernel<32><<<blocks, 256, 0, st>>>(a);
+    return check_launch("cn_knn_query");
 }
 
 extern "C" size_t cn_cloud_stats_workspace_bytes(int64_t Q) {

@@ -1057,6 +1057,126 @@ typedef struct cn_nn_query_desc {
 } cn_nn_query_desc;
 int cn_nn_query(const cn_nn_query_desc* d, cn_stream_t stream);
 
+/* cn_knn_query (additive to ABI v22): for each of Q queries the exact k nearest points of a
+ * built grid, 1 <= k <= 32, one lane per query: dist [Q][k] and index [Q][k].  A row is
+ * ascending under the total order (squared distance in fp32 as cn_nn_query forms it, original
+ * index) and holds exactly the k smallest pairs of that order among the targets with
+ * dist = sqrtf(d^2) < max_dist; a row with fewer such targets is padded with (max_dist, -1).
+ * count [Q] (or NULL) = the number found.  The shells and the stop rule are cn_nn_query's with
+ * the k-th best pair in place of the best (the proof: csrc/cn_mesh_eval.hip); at k = 1 the
+ * outputs are bitwise cn_nn_query's.  query_records as in cn_nn_query, with bitwise the same
+ * outputs either way.  exclude_self = 1 skips the target whose original index is the query's
+ * own (the query's position, or its record's index) -- exact duplicates at other indices are
+ * kept; it needs Q = N (CN_ERR_SHAPE otherwise).  A lane's list is kept in LDS as [slot][lane]
+ * (256 lanes x capacity x 8 bytes, capacity 8, 16 or 32: the smallest that holds k).
+ * No workspace. */
+typedef struct cn_knn_query_desc {
+    const cn_nn_grid_desc* grid;        /* HOST: a grid cn_nn_grid_build has filled */
+    int64_t Q;
+    const float* queries;               /* [Q][3], or [Q][4] records */
+    int32_t query_records;
+    float max_dist;                     /* >= 0, +inf allowed */
+    int32_t k;                          /* 1 .. 32 */
+    int32_t exclude_self;
+    float* dist;                        /* [Q][k] */
+    int32_t* index;                     /* [Q][k] */
+    int32_t* count;                     /* [Q], or NULL */
+} cn_knn_query_desc;
+int cn_knn_query(const cn_knn_query_desc* d, cn_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
+ * Point-cloud preparation (additive to ABI v22, csrc/cn_cloud.hip): what the protocols do to
+ * a raw scan before scoring -- voxel down-sampling, normals from the k nearest neighbours,
+ * and the sums of the statistical outlier filter.  No pass uses an atomic; each is bitwise
+ * repeatable.
+ *
+ * cn_voxel_keys: one thread per point.  Per axis f = fl(fl(p - origin) / voxel) in fp32
+ * (origin, voxel: HOST values, voxel > 0 and finite); where 0 <= f < 2^21 on all three axes
+ * keys[i] = (ix << 42) | (iy << 21) | iz with i = floor(f), valid[i] = 1; otherwise (a NaN or
+ * infinite coordinate, or one outside the 21-bit range) keys[i] = CN_VOXEL_KEY_NONE, which
+ * sorts after every voxel, and valid[i] = 0: such a point is dropped, never clamped into a
+ * voxel.  valid may be NULL.
+ *
+ * cn_voxel_reduce: keys [N] are cn_voxel_keys' sorted ascending by a STABLE sort and order [N]
+ * (int64) the original index of each sorted element.  Run heads are flagged and scanned (int32,
+ * the three-launch block scan of the point grid); one thread per voxel walks its run -- in
+ * ascending original index, the sort being stable -- and sums positions and, where given,
+ * normals and colors (fp32 [N][3] each) in double.  Voxel v, in ascending key order, gets
+ * out_points[v] = the fp32 of sum / count, out_colors[v] likewise, out_normals[v] = the fp32 of
+ * sum / |sum| in double (a zero or non-finite |sum|: a zero normal), out_counts[v], out_keys[v]
+ * (or NULL); totals (DEVICE int32 [2]) = (the number of voxels M, the points dropped).  The
+ * outputs are sized for N voxels; rows from M on are not written.  An order entry outside
+ * [0, N) gathers nothing.
+ * Workspace (256-byte aligned): 4 N (run starts) + 4 max(1, ceil(N / 1024)) (tile totals),
+ * each rounded up to 256 bytes.
+ *
+ * cn_cloud_normals: one thread per point over its neighbour row index [N][k] (cn_knn_query's
+ * over the cloud itself; 1 <= k <= 32).  Entries of -1 are skipped and entries outside [0, N)
+ * are skipped and never gathered.  The centroid, then the 3 x 3 covariance about it, of the
+ * valid neighbours in row order in double; the eigenvector of the smallest eigenvalue by
+ * cyclic Jacobi in double (at most 12 sweeps); normals [N][3] = that vector, unit, in fp32,
+ * and variation [N] (or NULL) = l0 / (l0 + l1 + l2).  The normal (and the variation) is zero
+ * with fewer than 3 valid neighbours, with a non-finite point or neighbour, and when
+ * l1 <= 1e-12 l2 (a collinear neighbourhood) -- what cn_cloud_normal_stats and
+ * cn_icp_accumulate leave out and count.  Sign: orient = 1 flips it so that
+ * n . (orient_to - p) >= 0 (orient_to: HOST, finite); orient = 0 makes the fp32 component of
+ * the largest magnitude positive, the first such component on a tie.  No workspace.
+ *
+ * cn_knn_mean_stats: mean [N] = per point the mean of the row's valid distances (dist [N][k]
+ * where index [N][k] >= 0) in row order in double, stored in fp32 (+inf for a row without
+ * one); out (DEVICE double [3]) = (the rows with a finite mean, the sum of those stored means,
+ * the sum of their squares) in cn_cloud_stats' fixed two-launch tree.  The host forms
+ * mu + ratio sigma.  Workspace (256-byte aligned): 24 blocks, rounded up to 256 bytes, blocks
+ * as cn_cloud_stats'.
+ * ------------------------------------------------------------------------ */
+#define CN_VOXEL_KEY_NONE INT64_MAX
+typedef struct cn_voxel_keys_desc {
+    int64_t N;
+    const float* points;                /* [N][3] */
+    float origin[3];
+    float voxel;
+    int64_t* keys;                      /* [N] */
+    int32_t* valid;                     /* [N], or NULL */
+} cn_voxel_keys_desc;
+int cn_voxel_keys(const cn_voxel_keys_desc* d, cn_stream_t stream);
+typedef struct cn_voxel_reduce_desc {
+    int64_t N;
+    const int64_t* keys;                /* [N], sorted */
+    const int64_t* order;               /* [N] */
+    const float* points;                /* [N][3] */
+    const float* normals;               /* [N][3], or NULL */
+    const float* colors;                /* [N][3], or NULL */
+    float* out_points;                  /* [N][3] */
+    float* out_normals;                 /* [N][3], with normals */
+    float* out_colors;                  /* [N][3], with colors */
+    int64_t* out_keys;                  /* [N], or NULL */
+    int32_t* out_counts;                /* [N] */
+    int32_t* totals;                    /* device [2] */
+} cn_voxel_reduce_desc;
+size_t cn_voxel_reduce_workspace_bytes(int64_t N);
+int cn_voxel_reduce(const cn_voxel_reduce_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+typedef struct cn_cloud_normals_desc {
+    int64_t N;
+    const float* points;                /* [N][3] */
+    const int32_t* index;               /* [N][k] */
+    int32_t k;
+    int32_t orient;
+    float orient_to[3];
+    float* normals;                     /* [N][3] */
+    float* variation;                   /* [N], or NULL */
+} cn_cloud_normals_desc;
+int cn_cloud_normals(const cn_cloud_normals_desc* d, cn_stream_t stream);
+typedef struct cn_knn_mean_stats_desc {
+    int64_t N;
+    int32_t k;
+    const float* dist;                  /* [N][k] */
+    const int32_t* index;               /* [N][k] */
+    float* mean;                        /* [N] */
+    double* out;                        /* device [3] */
+} cn_knn_mean_stats_desc;
+size_t cn_knn_mean_stats_workspace_bytes(int64_t N);
+int cn_knn_mean_stats(const cn_knn_mean_stats_desc* d, void* workspace, int64_t workspace_bytes, cn_stream_t stream);
+
 /* cn_cloud_stats: out (DEVICE double [4]) over dist [Q] (cn_nn_query's, with the same
  * max_dist) = (0) the points inside the crop box crop_min <= p <= crop_max (HOST values; all
  * Q when points is NULL), (1) those of them with dist < max_dist, (2) the sum of the

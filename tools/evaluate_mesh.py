@@ -7,7 +7,8 @@ precision / recall / F-score at a threshold in the Tanks and Temples style (metr
          [--cull-tol-rel R] [--cull-gt]] [--depths-out DIR] [--normal-maps-out DIR] [--culled-out MESH.ply]
         [--normals] [--gt-mesh-samples S] [--out results.txt]
         [--icp D [D ...] [--icp-mode point|plane] [--icp-scale] [--icp-samples S] [--icp-stride K [K ...]]
-         [--icp-max-iters N] [--icp-tol E] [--transform-out T.npy]]
+         [--icp-max-iters N] [--icp-tol E] [--transform-out T.npy] [--icp-voxel V]]
+        [--gt-outliers K RATIO] [--gt-voxel V] [--gt-estimate-normals K]
 
 MESH.ply is a triangle mesh (tools/extract_mesh.py's output as it is), GT.ply a point cloud (a mesh's vertices are
 taken as the cloud).  --transform is a 4 x 4 similarity applied to the mesh first.  --align-poses takes two
@@ -28,8 +29,12 @@ before the mesh is measured (metrics.icp_register_stages, as the Tanks-and-Templ
 alignment): one correspondence distance per stage, coarse to fine, on --icp-samples points drawn from the mesh
 (default 200000), every --icp-stride'th of them (one K for all stages or one per stage); --icp-mode plane takes its
 normals where --normals does (and so implies it), --icp-scale also fits a scale (point mode).  The icp_* entries and the composed
-transform follow the other entries; --transform-out saves the composed 4 x 4 (float64 .npy).  Prints one `name: value` line per
-metric and with --out writes them in metrics.write_results' format."""
+transform follow the other entries; --transform-out saves the composed 4 x 4 (float64 .npy).  A raw ground-truth scan is prepared
+first, in this order: --gt-outliers K RATIO removes its statistical outliers (mean distance to the K nearest
+neighbours above mean + RATIO std), --gt-voxel V voxel-down-samples it, --gt-estimate-normals K computes its normals
+from the K nearest neighbours -- which satisfies --normals and --icp-mode plane for a ground truth without normals.
+--icp-voxel V down-samples both clouds of the registration (not of the evaluation) to voxels of V.  Prints one
+`name: value` line per metric and with --out writes them in metrics.write_results' format."""
 import argparse
 import os
 import sys
@@ -133,7 +138,29 @@ def parse_args(argv=None):
     ap.add_argument("--icp-max-iters", type=int, default=50)
     ap.add_argument("--icp-tol", type=float, default=1e-6)
     ap.add_argument("--transform-out")
+    ap.add_argument("--gt-outliers", nargs=2, metavar=("K", "RATIO"))
+    ap.add_argument("--gt-voxel", type=float, metavar="V")
+    ap.add_argument("--gt-estimate-normals", type=int, metavar="K")
+    ap.add_argument("--icp-voxel", type=float, metavar="V")
     a = ap.parse_args(argv)
+    if a.gt_outliers is not None:
+        try:
+            a.gt_outliers = (int(a.gt_outliers[0]), float(a.gt_outliers[1]))
+        except ValueError:
+            ap.error("--gt-outliers takes a neighbour count K and a ratio")
+        if not 1 <= a.gt_outliers[0] <= 32 or not a.gt_outliers[1] > 0:
+            ap.error("--gt-outliers takes K in [1, 32] and a positive ratio")
+    if a.gt_voxel is not None and not (a.gt_voxel > 0 and a.gt_voxel < float("inf")):
+        ap.error("--gt-voxel takes a positive size")
+    if a.icp_voxel is not None and (a.icp is None or not (a.icp_voxel > 0 and a.icp_voxel < float("inf"))):
+        ap.error("--icp-voxel takes a positive size and needs --icp")
+    if a.gt_estimate_normals is not None:
+        if not 3 <= a.gt_estimate_normals <= 32:
+            ap.error("--gt-estimate-normals takes K in [3, 32]")
+        if not (a.normals or (a.icp is not None and a.icp_mode == "plane")):
+            ap.error("--gt-estimate-normals needs --normals or --icp-mode plane")
+    if a.gt_mesh_samples is not None and (a.gt_estimate_normals is not None or a.gt_outliers is not None):
+        ap.error("--gt-mesh-samples draws a clean cloud with the faces' normals: not with --gt-estimate-normals or --gt-outliers")
     if a.icp is None and (a.icp_stride is not None or a.icp_scale or a.transform_out or a.icp_mode != "point"):
         ap.error("--icp-mode, --icp-scale, --icp-stride and --transform-out need --icp")
     if a.icp is not None:
@@ -162,8 +189,9 @@ def icp_kwargs(a):
         return None
     strides = a.icp_stride or [1]
     strides = strides * len(a.icp) if len(strides) == 1 else strides
+    extra = {} if a.icp_voxel is None else {"voxel": a.icp_voxel}
     return dict(stages=[dict(max_corr_dist=d, stride=k) for d, k in zip(a.icp, strides)], n_samples=a.icp_samples,
-                mode=a.icp_mode, with_scale=a.icp_scale, max_iters=a.icp_max_iters, tol=a.icp_tol)
+                mode=a.icp_mode, with_scale=a.icp_scale, max_iters=a.icp_max_iters, tol=a.icp_tol, **extra)
 
 
 def main(argv=None):
@@ -176,7 +204,8 @@ def main(argv=None):
     if triangles is None:
         raise SystemExit(f"evaluate_mesh: {a.mesh} has no faces")
     want_normals = a.normals or (a.icp is not None and a.icp_mode == "plane")
-    gt, gt_triangles, gt_normals = load_ground_truth(a.gt, want_normals, a.gt_mesh_samples)
+    # (--gt-estimate-normals: the ground truth's normals are computed from its points, whatever the file holds)
+    gt, gt_triangles, gt_normals = load_ground_truth(a.gt, want_normals and a.gt_estimate_normals is None, a.gt_mesh_samples)
     transform = None
     if a.transform:
         transform = np.load(a.transform)
@@ -216,6 +245,9 @@ def main(argv=None):
         cull["gt_normals"] = gt_normals
     if a.icp is not None:
         cull["icp"] = icp_kwargs(a)
+    for key, value in (("gt_outliers", a.gt_outliers), ("gt_voxel", a.gt_voxel), ("gt_estimate_normals", a.gt_estimate_normals)):
+        if value is not None:
+            cull[key] = value
     result = metrics.mesh_geometry_metrics(
         tv, tf, gt_points, threshold=a.threshold, max_dist=a.max_dist, n_samples=a.samples,
         density=a.density, seed=a.seed, transform=transform, crop_min=a.crop_min, crop_max=a.crop_max, **cull)
