@@ -111,6 +111,26 @@ def test_argument_validation_without_gpu():
 
 
 
+def test_ray_kernels_refuse_depths_they_cannot_hold():
+    """cn_composite_fwd / cn_composite_bwd hold 1 <= S <= 256 samples per ray, cn_up_sample_merge 2 <= n,
+    1 <= n_imp <= 64 and n + n_imp <= 256: anything else is CN_ERR_UNSUPPORTED before any launch (the
+    placeholder pointers are never dereferenced)."""
+    from copenerf import _lib
+    lib = _lib.load()
+    p = 4096
+    for S, want in ((0, -5), (257, -5)):
+        assert lib.cn_composite_fwd(1, S, p, p, p, 4, p, p, p, p, p, 64, p, p, p, p, p, None) == want
+        assert b"cn_composite_fwd: S=%d" % S in lib.cn_last_error()
+        assert lib.cn_composite_bwd(1, S, p, p, p, 4, p, p, p, p, p, 64, p, p, p, p, p, p, p, p, p, p, None) == want
+        assert b"cn_composite_bwd: S=%d" % S in lib.cn_last_error()
+    for n, n_imp in ((1, 16), (64, 0), (64, 65), (193, 64), (241, 16)):
+        assert lib.cn_up_sample_merge(1, n, n_imp, 64.0, p, p, p, p, None, None, None) == -5, (n, n_imp)
+        assert b"cn_up_sample_merge: n=%d n_imp=%d" % (n, n_imp) in lib.cn_last_error()
+    # and with nothing to do (R = 0) the accepted extremes return before launching as well
+    assert lib.cn_composite_fwd(0, 256, p, p, p, 4, p, p, p, p, p, 64, p, p, p, p, p, None) == 0
+    assert lib.cn_up_sample_merge(0, 192, 64, 64.0, p, p, p, p, None, None, None) == 0
+
+
 def _fake_net(mode=1, dh=256, multires=6, skip=4):
     """A cn_sdf_net of SDFNetwork(d_hidden=dh, n_layers=8, skip_in=[skip]) with placeholder (aligned,
     never dereferenced) pointers: host planning only."""

@@ -120,6 +120,34 @@ def test_c_sample_equals_renderer_and_layered_query(mode):
     assert bool((z[:, 1:] >= z[:, :-1]).all())  # merged in order
 
 
+def test_c_sample_matches_composition_at_a_ragged_configuration():
+    """n_samples 24, n_importance 40 in 5 rounds of 8 (depths 24, 32, ... 64: no round's interval count is a
+    multiple of the wavefront), 7 rays (a ragged block), fp32, d_hidden 64: cn_sample gives the bits of the
+    launch-by-launch composition, sorted, with the coarse samples among them."""
+    from copenerf import NeuSRenderer
+    sdf, col, dev = build_modules(9, dh_sdf=64, dh_col=64, device=DEV)
+    r = NeuSRenderer(None, sdf, dev, col, None, **dict(REN_CFG, n_samples=24, n_importance=40,
+                                                       up_sample_steps=5)).to(DEV).set_mfma_dtype("fp32")
+    gen = torch.Generator(device=DEV).manual_seed(17)
+    R = 7
+    rays_o = (torch.rand(R, 3, device=DEV, generator=gen) - 0.5) * 0.4
+    rays_d = torch.nn.functional.normalize(torch.randn(R, 3, device=DEV, generator=gen), dim=-1)
+    near = torch.full((R, 1), 0.2, device=DEV)
+    far = torch.full((R, 1), 1.8, device=DEV)
+    t = torch.full((1,), -0.3, device=DEV)
+    t_rand = torch.rand(R, r.n_samples, device=DEV, generator=gen)
+    with torch.no_grad():
+        pk = r.sdf_network.params_and_pack()[2]
+        z = _c_sample(r, pk, rays_o, rays_d, t, near, far, t_rand)
+        zc = _composed(r, pk, rays_o, rays_d, t, near, far, t_rand)
+    assert z.shape == (R, 64) and torch.equal(z, zc), (z - zc).abs().max().item()
+    assert bool((z[:, 1:] >= z[:, :-1]).all())
+    coarse = torch.empty(R, 24, device=DEV)
+    from copenerf import ops
+    ops.coarse_z(near, far, 24, t_rand, coarse)
+    assert bool((coarse[:, :, None] == z[:, None, :]).any(-1).all())
+
+
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("dh", [256, 64])
 def test_c_sdf_query_matches_sdf_forward(mode, dh):
